@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the fused EKS hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4] [--full]
+                    [--dump-outputs DIR]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -26,10 +27,18 @@ Synthetic data: seeded random walks / AR(1) latents, member
 noise sigma_e ~ U(0.5, 3) px, 1 % outliers of 30 px (single/multi-view);
 values float32.
 
-Prints ONE JSON line (rank 0): throughput, the roofline of the smoother's
-kernels (HIP events recorded by libeks_hip on the launch stream), the CPU
-baseline (the numpy oracle on a bounded sample, 1 core) and max|d| between
-the GPU and CPU outputs on that sample.
+Prints ONE JSON line (rank 0).  A plain run does only what the headline
+figure needs: set-up, warm-up, the K timed steps, and the line with the
+throughput (``value``), ``ms_per_step`` and the HBM roofline on the step time.
+``--full`` adds the measurements that take runs of their own: the per-kernel
+times (HIP events recorded by libeks_hip on the launch stream), the end-to-end
+loop with the device fit, the N > 1 gather, the CPU baseline (the numpy
+oracle on a bounded sample, 1 core and all cores) and max|d| between the GPU
+and CPU outputs on that sample.
+
+``--dump-outputs DIR`` writes what the last timed step computed (the arrays a
+caller of the timed path receives) to DIR/<name>.npy right after the timed
+loop; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -46,6 +55,9 @@ sys.path.insert(0, HERE)
 METRIC = "keypoint-timesteps smoothed/sec at 1/2/4/8 MI355X; max|Δ| vs CPU"
 PEAK_HBM_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 PEAK_FP64_TFS = 78.6   # MI355X FP64 vector peak (AMD spec: half the 157.3 TF/s FP32 vector rate)
+# --dump-outputs: at most 3 large arrays per workload (out, ms, ...), 64 MB in all
+DUMP_ARRAY_BYTES = 16 << 20
+DUMP_SEED = 20240229
 
 
 def parse():
@@ -69,9 +81,18 @@ def parse():
     ap.add_argument("--cpu-cores", type=int, default=None,
                     help="processes of the all-core CPU baseline (default: the affinity mask, "
                          "capped by OMP_NUM_THREADS)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel timing pass, the "
+                         "end-to-end (fit + smooth) loop, the N > 1 gather and the CPU baseline "
+                         "with its max|d| check (a plain run skips them all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64; "
+                         f"arrays over {DUMP_ARRAY_BYTES >> 20} MiB as a fixed seeded sample of "
+                         "their trajectories / frames)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true",
-                    help="config 4, N > 1: skip the final gather of all outputs to rank 0 "
+                    help="--full, config 4, N > 1: skip the final gather of all outputs to rank 0 "
                          "(RCCL), timed once after the throughput loop")
     ap.add_argument("--dense-pupil", action="store_true",
                     help="config 5: run the pupil model through the dense r=3, n=8 kernels "
@@ -87,6 +108,8 @@ def parse():
                     help="config 4: strong = the video batch is split over ranks; weak = "
                          "every rank smooths --videos videos")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     a.frames = a.frames or {4: 10000, 2: 100000, 3: 50000, 5: 1000000}[a.config]
     a.seed = a.config if a.seed is None else a.seed
     return a
@@ -320,7 +343,7 @@ def workload_singleview(torch, a, dev, rank, world, config):
                 # rank's own shard (videos per rank), so an N-rank line finds
                 # the profile of an N = 1 run of the same shard size
                 key=f"config{config}-singleview-v{len(videos)}-k{K}-e{E}-t{T}",
-                out=out, videos=videos)
+                out=out, videos=videos, outputs=lambda: dict(out=out, status=status))
 
 
 def workload_multiview(torch, a, dev, rank, world):
@@ -369,7 +392,8 @@ def workload_multiview(torch, a, dev, rank, world):
                 cfg=dict(cameras=V, keypoints=K, members=E, frames=T,
                          smooth_param=a.smooth_param, quantile_keep=a.quantile_keep),
                 shape=(K, T, n, 3, E),
-                key=f"config3-multiview-k{K}-e{E}-t{T}" + (f"-v{V}" if V != 4 else ""))
+                key=f"config3-multiview-k{K}-e{E}-t{T}" + (f"-v{V}" if V != 4 else ""),
+                outputs=lambda: dict(out=out, status=status))
 
 
 def workload_pupil(torch, a, dev, rank, world):
@@ -484,6 +508,10 @@ def workload_pupil(torch, a, dev, rank, world):
                 cfg=dict(frames=T, keypoints=4, members=E, candidates=len(cands)),
                 shape=(1, T, 8, 3, E),
                 key=f"config5-pupil-t{T}" + (f"-ts-n{world}" if a.timeshard else ""),
+                # the step's results: the candidates' NLL, the argmin, and the
+                # chosen model's smoothed markers / latents (this rank's frames)
+                outputs=lambda: dict(out=out[:, t0:t0 + Tk], ms=state["ms"], nll=state["scores"],
+                                     best=state["best"], status=status),
                 extra=lambda: dict(
                     sweep_candidates=len(cands),
                     best_model=[float(x) for x in np.diag(cands[int(state['best'])]['A'])]))
@@ -502,6 +530,40 @@ def assert_clean(torch, w, where):
                            "promise broken, 4 scan / chain-wait breakdown)")
     if "post_check" in w:
         w["post_check"]()
+
+
+def dump_sample(shape, dim, keep):
+    """Sorted indices of the ``keep`` entries of dimension ``dim`` that
+    --dump-outputs stores of an array of this shape: a function of the shape
+    alone (fixed seed), so two builds store the same entries."""
+    import numpy as np
+    rng = np.random.default_rng([DUMP_SEED, dim, *shape])
+    return np.sort(rng.choice(shape[dim], size=keep, replace=False))
+
+
+def dump_outputs(torch, arrays, dirpath, rank=0):
+    """Write each tensor of ``arrays`` to dirpath/<name>.npy as float64 (rank
+    r > 0: <name>.rank<r>.npy, its own shard).  An array above
+    DUMP_ARRAY_BYTES is cut to a seeded sample of whole trajectories (dim 0),
+    then, if one trajectory is still too large, of its frames (dim 1).
+    Returns {file name: shape written}."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        for dim in range(min(t.dim(), 2)):
+            nbytes = t.numel() * 8
+            if nbytes <= DUMP_ARRAY_BYTES:
+                break
+            keep = max(1, t.shape[dim] * DUMP_ARRAY_BYTES // nbytes)
+            idx = torch.as_tensor(dump_sample(tuple(t.shape), dim, keep), device=t.device)
+            t = t.index_select(dim, idx)
+        arr = np.ascontiguousarray(t.to(torch.float64).cpu().numpy())
+        fname = name + ("" if rank == 0 else f".rank{rank}") + ".npy"
+        np.save(os.path.join(dirpath, fname), arr)
+        written[fname] = list(arr.shape)
+    return written
 
 
 def load_pmc(workload_key, path=None):
@@ -535,9 +597,9 @@ def launch_ranks(a) -> int:
 
 
 def runs_cpu_baseline(rank, a) -> bool:
-    """The CPU baseline runs on rank 0's own shard after the timed loop, at
-    any N (for N > 1 the other ranks wait at the final barrier)."""
-    return rank == 0 and not a.no_cpu_baseline
+    """The CPU baseline (--full) runs on rank 0's own shard after the timed
+    loop, at any N (for N > 1 the other ranks wait at the final barrier)."""
+    return rank == 0 and a.full and not a.no_cpu_baseline
 
 
 def make_line(a, w, world, algo_used, units_local, units_total, elapsed_max, kernels,
@@ -553,7 +615,9 @@ def make_line(a, w, world, algo_used, units_local, units_total, elapsed_max, ker
     # memset node and the launch gaps the replay pays)
     step_ms = elapsed_max / a.steps * 1e3
     achieved = w["bytes_per_unit"] * units_local / (step_ms * 1e-3) / 1e9
-    achieved_ev = w["bytes_per_unit"] * units_local / (kern_ms_max * 1e-3) / 1e9
+    # (a plain run has no kernel-timing pass: kernels is None, and the
+    # per-kernel fields of the roofline block are left out)
+    full = kernels is not None
     pmc = load_pmc(w["key"], pmc_path)
     scaling = ("strong" if (a.config == 4 and a.scaling == "strong") or w.get("timeshard")
                else "weak")
@@ -582,12 +646,7 @@ def make_line(a, w, world, algo_used, units_local, units_total, elapsed_max, ker
             "frac": achieved / PEAK_HBM_GBS,
             "traffic": (pmc or {}).get("hbm_bytes_per_launch"),
             "traffic_key": w["key"],
-            "kernel": "eks_smooth (" + " + ".join(n for n, _ in kernels) + ")",
             "time_basis": "ms_per_step (graph replay)",
-            "kernel_ms": kern_ms_max,
-            "achieved_kernel_events": achieved_ev,
-            "frac_kernel_events": achieved_ev / PEAK_HBM_GBS,
-            "kernels_ms": {n: round(ms, 4) for n, ms in kernels},
             "bytes_per_unit": w["bytes_per_unit"],
             "units_per_launch": units_local,
         },
@@ -596,8 +655,18 @@ def make_line(a, w, world, algo_used, units_local, units_total, elapsed_max, ker
         "end_to_end": None if e2e is None else dict(e2e, cpu_value=cpu_e2e),
         "setup_s": round(setup_s, 2),
         "hip_graph": hip_graph,
+        "full": full,
     }
-    if "flops" in w:  # an FP64-issue-bound kernel: its flop roofline beside the HBM one
+    if full:
+        achieved_ev = w["bytes_per_unit"] * units_local / (kern_ms_max * 1e-3) / 1e9
+        line["roofline"].update({
+            "kernel": "eks_smooth (" + " + ".join(n for n, _ in kernels) + ")",
+            "kernel_ms": kern_ms_max,
+            "achieved_kernel_events": achieved_ev,
+            "frac_kernel_events": achieved_ev / PEAK_HBM_GBS,
+            "kernels_ms": {n: round(ms, 4) for n, ms in kernels},
+        })
+    if full and "flops" in w:  # an FP64-issue-bound kernel: its flop roofline beside the HBM one
         f = w["flops"]
         kms = dict(kernels).get(f["kernel"])
         if kms:
@@ -627,7 +696,6 @@ def main():
         sys.exit(launch_ranks(a))
     import torch
     from eks_amd import _lib, dist
-    from threadpoolctl import threadpool_limits
     rank, world, local = dist.init()
     if world != a.gpus and rank == 0:
         print(f"[bench] note: --gpus {a.gpus} but WORLD_SIZE={world}; using {world}",
@@ -697,23 +765,31 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed_max = dist.max_over_ranks(elapsed, device=dev)
     assert_clean(torch, w, "timed loop")
+    # what the last timed step left in the step's output buffers, before any
+    # later loop writes them again
+    dumped = None
+    if a.dump_outputs:
+        dumped = dump_outputs(torch, w["outputs"](), a.dump_outputs, rank)
+    units_local = w["units"]
+    units_total = dist.sum_over_ranks(units_local, device=dev)
     # per-kernel launch durations: HIP events recorded by libeks_hip on the
     # launch stream around each kernel of each eks_smooth call (separate pass,
     # so the events do not perturb the timed loop above)
-    _lib.profile_begin(8 * a.steps)
-    for _ in range(a.steps):
-        eager_step()
-    kernels = [(n, ms / a.steps) for n, ms in _lib.profile_end()]  # per step
-    assert_clean(torch, w, "kernel-timing loop")
-    kern_ms = sum(ms for _, ms in kernels)
-    kern_ms_max = dist.max_over_ranks(kern_ms, device=dev)
-    units_local = w["units"]
-    units_total = dist.sum_over_ranks(units_local, device=dev)
+    kernels = None
+    kern_ms_max = None
+    if a.full:
+        _lib.profile_begin(8 * a.steps)
+        for _ in range(a.steps):
+            eager_step()
+        kernels = [(n, ms / a.steps) for n, ms in _lib.profile_end()]  # per step
+        assert_clean(torch, w, "kernel-timing loop")
+        kern_ms = sum(ms for _, ms in kernels)
+        kern_ms_max = dist.max_over_ranks(kern_ms, device=dev)
 
     # end to end: the model fit on the device (eks_fit) + the hot path, i.e.
     # what the reference's per-keypoint wrappers do from member predictions
     e2e = None
-    if "fit_step" in w:
+    if a.full and "fit_step" in w:
         fit_step, e2e_smooth = w["fit_step"], w["e2e_smooth"]
 
         def e2e_eager():
@@ -768,7 +844,7 @@ def main():
     # RCCL, timed once after the throughput loop, never inside ``value``
     gather_ms = None
     gather_bytes = None
-    if not a.no_gather and world > 1 and a.config == 4:
+    if a.full and not a.no_gather and world > 1 and a.config == 4:
         T, K = a.frames, a.keypoints
         nv = len(w["videos"])
         loc = w["out"].permute(1, 0, 2).reshape(T, nv, K, 2).permute(1, 0, 2, 3).contiguous()
@@ -832,6 +908,8 @@ def main():
         if nll_rel is not None:
             line["nll_rel_diff_vs_cpu"] = nll_rel
         line["warmup_replays"] = warm_replays
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line))
     dist.barrier()
 

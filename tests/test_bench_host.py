@@ -85,13 +85,56 @@ def test_cpu_task_kinds_match_oracle_smoothers():
     np.testing.assert_array_equal(outs[2], O.singleview_smooth(tasks[2][1], 0.01, 25.0)[0])
 
 
+def test_plain_run_skips_what_full_adds(monkeypatch):
+    """Without --full the CPU baseline is off and the line carries the
+    headline fields with the step-time roofline, no per-kernel block."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None
+    assert not bench.runs_cpu_baseline(0, a)
+    w = dict(key="k", desc="d", cfg={}, bytes_per_unit=56, units=1000)
+    line = bench.make_line(a, w, 1, 3, 1000, 1000, 0.002 * a.steps, None, None, None, None,
+                           None, None, None, None, 1.0, True, None)
+    assert line["steps"] == 4 and line["ms_per_step"] == pytest.approx(2.0)
+    assert line["value"] == pytest.approx(1000 / 0.002)
+    assert (line["metric"], line["unit"], line["dtype"]) == (bench.METRIC, "kp-ts/s", "f64")
+    assert line["higher_is_better"] is True and line["full"] is False
+    assert line["roofline"]["achieved"] == pytest.approx(56 * 1000 / 0.002 / 1e9)
+    assert "kernels_ms" not in line["roofline"] and line["cpu_baseline"] is None
+    with pytest.raises(SystemExit):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+        bench.parse()
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole, large ones cut to the same seeded
+    trajectories on every call, everything float64."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 4096)
+    out = torch.arange(40 * 64 * 2, dtype=torch.float64).reshape(64, 40, 2).permute(1, 0, 2)
+    long_ = torch.arange(2000 * 3, dtype=torch.float64).reshape(1, 2000, 3)
+    status = torch.zeros(40, dtype=torch.int32)
+    arrays = dict(out=out, ms=long_, status=status)
+    w1 = bench.dump_outputs(torch, arrays, str(tmp_path / "a"))
+    w2 = bench.dump_outputs(torch, arrays, str(tmp_path / "b"), rank=1)
+    assert w1 == {"out.npy": [4, 64, 2], "ms.npy": [1, 170, 3], "status.npy": [40]}
+    assert sorted(w2) == ["ms.rank1.npy", "out.rank1.npy", "status.rank1.npy"]
+    for name in ("out", "ms", "status"):
+        x = np.load(tmp_path / "a" / f"{name}.npy")
+        assert x.dtype == np.float64 and x.nbytes <= 4096
+        np.testing.assert_array_equal(x, np.load(tmp_path / "b" / f"{name}.rank1.npy"))
+    rows = bench.dump_sample((40, 64, 2), 0, 4)
+    assert list(rows) == sorted(set(rows)) and len(rows) == 4
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "out.npy"), out.numpy()[rows])
+
+
 def test_multi_rank_line_schema(tmp_path, monkeypatch):
     """An N > 1 line (the driver's SCALE runs) carries the CPU baseline (rank
     0's shard), the PMC traffic of one rank's launch (looked up by the
     per-rank shard key, i.e. the entry an N = 1 run of that shard size
     wrote), the distributed block and the timed RCCL gather."""
     import json
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--full"])
     a = bench.parse()
     assert bench.runs_cpu_baseline(0, a) and not bench.runs_cpu_baseline(1, a)
     key = "config4-singleview-v128-k17-e5-t10000-a3"

@@ -1,12 +1,12 @@
 #!/bin/bash
 # configs x forced chunk length (EKS_CHUNK_LEN; 0 = the default rule)
 set -o pipefail
-mkdir -p gpurun_out
+mkdir -p ${EKS_OUT:-bench_out}
 for L in ${LENS:-0 16 32 64}; do
   if [ $L = 0 ]; then unset EKS_CHUNK_LEN; else export EKS_CHUNK_LEN=$L; fi
   for c in ${CONFIGS:-3 5 2}; do
-    timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/c${c}_L$L.log 2>&1 || exit $?
-    python - gpurun_out/c${c}_L$L.log $c $L <<'PY'
+    timeout -k 10 300 python bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline > ${EKS_OUT:-bench_out}/c${c}_L$L.log 2>&1 || exit $?
+    python - ${EKS_OUT:-bench_out}/c${c}_L$L.log $c $L <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 k = d["roofline"]["kernels_ms"]

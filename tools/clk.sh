@@ -5,17 +5,17 @@
 #   VARIANTS="r05 default" BENCH_ARGS="--videos 1024" bash tools/clk.sh
 set -o pipefail
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
-mkdir -p gpurun_out/clk
+mkdir -p ${EKS_OUT:-bench_out}/clk
 for v in ${VARIANTS:-default}; do
   if [ "$v" = default ]; then unset EKS_LIB; else export EKS_LIB=exp/$v/libeks_hip.so; fi
   rm -rf /tmp/clk_$v
   timeout -s KILL 120 rocprofv3 --kernel-include-regex 'k3_' --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU \
-      -d /tmp/clk_$v -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 \
-      --no-cpu-baseline --no-graph ${BENCH_ARGS} > gpurun_out/clk/$v.log 2>&1 || { echo "rocprof failed $v"; tail -5 gpurun_out/clk/$v.log; exit 1; }
+      -d /tmp/clk_$v -o run --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 \
+      --no-cpu-baseline --no-graph ${BENCH_ARGS} > ${EKS_OUT:-bench_out}/clk/$v.log 2>&1 || { echo "rocprof failed $v"; tail -5 ${EKS_OUT:-bench_out}/clk/$v.log; exit 1; }
   for f in $(find /tmp/clk_$v -name "*counter_collection.csv" -o -name "*kernel_trace.csv"); do
-    cp $f gpurun_out/clk/${v}_$(basename $f)
+    cp $f ${EKS_OUT:-bench_out}/clk/${v}_$(basename $f)
   done
-  python3 - gpurun_out/clk/${v}_run_counter_collection.csv $v <<'PY'
+  python3 - ${EKS_OUT:-bench_out}/clk/${v}_run_counter_collection.csv $v <<'PY'
 import csv, sys
 from collections import defaultdict
 per = defaultdict(float); dur = {}

@@ -3,7 +3,7 @@
 # for each library variant: default = eks_amd/lib, NAME = exp/NAME.
 #   VARIANTS="r05 default" bash tools/configs.sh
 set -o pipefail
-mkdir -p gpurun_out/cfg
+mkdir -p ${EKS_OUT:-bench_out}/cfg
 export PYTHONDONTWRITEBYTECODE=1
 CASES=${CASES:-"c2:--config 2|c3:--config 3|c3v6:--config 3 --cameras 6|c3v8:--config 3 --cameras 8|c5:--config 5"}
 IFS='|' read -ra CS <<< "$CASES"
@@ -11,8 +11,8 @@ for v in ${VARIANTS:-default}; do
   if [ "$v" = default ]; then unset EKS_LIB; else export EKS_LIB=exp/$v/libeks_hip.so; fi
   for c in "${CS[@]}"; do
     tag=${c%%:*}; args=${c#*:}
-    log=gpurun_out/cfg/${v}_$tag.log
-    timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline $args > $log 2>&1 \
+    log=${EKS_OUT:-bench_out}/cfg/${v}_$tag.log
+    timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline $args > $log 2>&1 \
       || { echo "bench failed: $log"; tail -5 $log; exit 1; }
     python - $log "$v $tag" <<'PY'
 import json, sys

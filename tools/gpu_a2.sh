@@ -2,7 +2,7 @@
 # algo 2 (few long trajectories) check: its GPU tests, then configs 2 / 3 / 5
 # bench lines (optionally a chunk-length sweep: LENS="8 16 ...").
 set -o pipefail
-OUT=gpurun_out/${TAG:-a2}
+OUT=${EKS_OUT:-bench_out}/${TAG:-a2}
 mkdir -p $OUT
 export PYTHONDONTWRITEBYTECODE=1
 if [ -z "$NOTEST" ]; then
@@ -13,7 +13,7 @@ fi
 for c in ${CFGS:-2 3 5}; do
   for L in ${LENS:-0}; do
     if [ "$L" = 0 ]; then unset EKS_CHUNK_LEN; else export EKS_CHUNK_LEN=$L; fi
-    timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline > $OUT/c${c}_L$L.log 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline > $OUT/c${c}_L$L.log 2>&1 || exit $?
     python - $OUT/c${c}_L$L.log "c=$c L=$L" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # A/B of library variants on config 4 (bench lines, kernel times):
 #   LIBS="default exp/r03/libeks_hip.so ..." VIDEOS="1024 128" bash tools/gpu_ab.sh
 set -o pipefail
-OUT=gpurun_out/${TAG:-ab}
+OUT=${EKS_OUT:-bench_out}/${TAG:-ab}
 mkdir -p $OUT
 export PYTHONDONTWRITEBYTECODE=1
 if [ -n "$TESTS" ]; then
@@ -14,7 +14,7 @@ for lib in ${LIBS:-default}; do
   i=$((i+1))
   for nv in ${VIDEOS:-1024 128}; do
     if [ "$lib" = "default" ]; then unset EKS_LIB; else export EKS_LIB=$lib; fi
-    timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --videos $nv $BENCH_ARGS > $OUT/b${i}_v$nv.log 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --videos $nv $BENCH_ARGS > $OUT/b${i}_v$nv.log 2>&1 || exit $?
     python - $OUT/b${i}_v$nv.log "$lib" $nv <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -25,7 +25,7 @@ PY
 done
 unset EKS_LIB
 for c in ${CONFIGS-}; do
-  timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_c$c.log 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_c$c.log 2>&1 || exit $?
   python - $OUT/bench_c$c.log $c <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

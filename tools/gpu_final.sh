@@ -7,7 +7,7 @@
 set -o pipefail
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 TAG=${TAG:-r06}
-O=gpurun_out/final_$TAG; mkdir -p $O
+O=${EKS_OUT:-bench_out}/final_$TAG; mkdir -p $O
 PART=${PART:-all}  # bench | prof | all (each part stays under gpurun's 64 MiB copy-back)
 summ() { python - "$1" "$2" <<'PY'
 import json, sys
@@ -23,17 +23,17 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-me
 rc=$?; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python -c "import time, ctypes; t = time.time(); ctypes.CDLL('eks_amd/lib/libeks_hip.so'); print('dlopen s', round(time.time() - t, 3))" && timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
 tail -2 $O/smoke.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench_default.log 2>&1 || exit $?
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.log 2>&1 || exit $?
 tail -c 300 $O/bench_default.log; echo
 summ $O/bench_default.log default
 for c in "4 --videos 128" "4 --videos 256" "2" "3" "3 --cameras 6" "3 --cameras 8" "5"; do
   name=$(echo "c$c" | tr -d ' -')
-  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.log 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.log 2>&1 || exit $?
   summ $O/bench_$name.log $name
 done
 for lib in default; do
   if [ $lib = default ]; then unset EKS_LIB; else export EKS_LIB=exp/$lib/libeks_hip.so; fi
-  timeout -k 10 300 python bench.py --frames 4000 --steps 20 --warmup 5 --no-cpu-baseline > $O/t4000_$lib.log 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full --frames 4000 --steps 20 --warmup 5 --no-cpu-baseline > $O/t4000_$lib.log 2>&1 || exit $?
   summ $O/t4000_$lib.log t4000_$lib
 done
 unset EKS_LIB

@@ -8,14 +8,14 @@ set -o pipefail
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
 TAG=${TAG:-pmc}
 RAW=/tmp/pmc_$TAG
-OUT=gpurun_out/pmc_$TAG
+OUT=${EKS_OUT:-bench_out}/pmc_$TAG
 mkdir -p $OUT $RAW
 RX=${RX:-'k3_'}
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
 pass() {  # name, counters...
   local name=$1; shift
   timeout -s KILL 120 rocprofv3 --kernel-include-regex "$RX" --pmc "$@" -d $RAW/$name -o run \
-      --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph \
+      --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph \
       ${BENCH_ARGS} > $OUT/$name.log 2>&1
   local rc=$?
   echo "$name rc=$rc ($*)" >> $OUT/status.txt

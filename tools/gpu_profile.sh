@@ -6,12 +6,12 @@ set -o pipefail
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
 TAG=${1:-r01}
 RAW=/tmp/prof_$TAG
-OUT=gpurun_out/prof_$TAG
+OUT=${EKS_OUT:-bench_out}/prof_$TAG
 mkdir -p $OUT $RAW
 step() {  # name, timeout, rocprof args...
   local name=$1 t=$2; shift 2
   timeout -k 10 $t rocprofv3 "$@" -d $RAW/$name -o run --output-format csv -- \
-      python3 bench.py --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/$name.log 2>&1
+      python3 bench.py --full --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/$name.log 2>&1
   local rc=$?
   echo "$name rc=$rc" >> $OUT/status.txt
   (cd $RAW && find $name -type f -printf "%s %p\n") >> $OUT/files.txt

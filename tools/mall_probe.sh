@@ -1,8 +1,8 @@
 set -o pipefail
 export PYTHONDONTWRITEBYTECODE=1
 for nv in 8 16 32 64 1024; do
-  timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --videos $nv --algo 3 > gpurun_out/mall_$nv.log 2>&1 || exit $?
-  python - gpurun_out/mall_$nv.log $nv <<'PY'
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --videos $nv --algo 3 > ${EKS_OUT:-bench_out}/mall_$nv.log 2>&1 || exit $?
+  python - ${EKS_OUT:-bench_out}/mall_$nv.log $nv <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 k = d["roofline"]["kernels_ms"]; u = d["roofline"]["units_per_launch"]

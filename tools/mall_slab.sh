@@ -6,12 +6,12 @@
 # batch, so a resident batch is re-read from the MALL by BOTH member passes.
 set -o pipefail
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
-OUT=gpurun_out/${TAG:-mall}
+OUT=${EKS_OUT:-bench_out}/${TAG:-mall}
 mkdir -p $OUT
 for nv in ${VIDEOS:-16 64 1024}; do
-  timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --videos $nv --algo 3 > $OUT/bench_v$nv.log 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --videos $nv --algo 3 > $OUT/bench_v$nv.log 2>&1 || exit $?
   timeout -s KILL 120 rocprofv3 --kernel-include-regex 'k3_' --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum \
-      -d /tmp/mall_v$nv -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --videos $nv --algo 3 > $OUT/pmc_v$nv.log 2>&1 || exit $?
+      -d /tmp/mall_v$nv -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --videos $nv --algo 3 > $OUT/pmc_v$nv.log 2>&1 || exit $?
   f=$(find /tmp/mall_v$nv -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] || { echo "no counter file for $nv videos"; exit 1; }
   python3 - "$f" $nv $OUT/bench_v$nv.log >> $OUT/summary.txt <<'PY'
