@@ -652,7 +652,7 @@ __global__ __launch_bounds__(BLK, KPT > 0 ? EKS_SEL_KPT_WPE : EKS_SEL_WPE) void 
       above_in_bin = su[1];
       __syncthreads();
     }
-  } else if constexpr (kPacked) {  // the 8 KB histogram holds 2 048 bins: 8-bit digits
+  } else if constexpr (kPacked) {  // hist: 16 KB, 8 192 packed bins; hsel: 256-bin digits
     ka = block_select<BLK, kSelDigit>(keys, TT, lo, 62, 0ull, hsel, su, si);
   } else {
     ka = block_select<BLK>(keys, TT, lo, 62, 0ull, hist, su, si);

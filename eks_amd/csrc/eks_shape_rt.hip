@@ -289,14 +289,10 @@ __global__ __launch_bounds__(kBlock) void k_rt_c3(SmoothArgs a, ChunkPlan p) {
   const YT *ybuf = (const YT *)p.ysrc;
   const double *evbuf = (const double *)p.evsrc;
   double *jdp = (double *)(a.ws + p.jd_off);
-  double m[R], P[R][R], G[R][R], g[R];
+  double m[R], P[R][R];
   load_state_pl<R>((const double *)(a.ws + p.cstart_off), c * KS, B, b, m, P);
-#pragma unroll
-  for (int i = 0; i < R; ++i) {
-    g[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < R; ++j) G[i][j] = (i == j) ? 1.0 : 0.0;
-  }
+  Affine<R> F;  // the chunk's RTS map
+  F.set_identity();
   const long long s = c * p.L, e = min(TT, s + p.L);
   bool ok = true;
   NllAcc acc;
@@ -329,31 +325,13 @@ __global__ __launch_bounds__(kBlock) void k_rt_c3(SmoothArgs a, ChunkPlan p) {
       }
     }
     store_jd<R>(jdp, t, B, b, J, d);
-    double GJ[R][R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      double sg = g[i];
-#pragma unroll
-      for (int u = 0; u < R; ++u) sg = fma(G[i][u], d[u], sg);
-      g[i] = sg;
-    }
-    matmul<R, R, R>(G, J, GJ);
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-#pragma unroll
-      for (int k = 0; k < R; ++k) G[i][k] = GJ[i][k];
+    F.then(J, d);  // (the last step too, as J = 0: not then_const)
   };
   rt_columns(s, e, n, fetch, col, begin, end);
   pl((double *)(a.ws + p.nllp_off), c, B, b) = acc.value((double)(e - s) * n);
   if (!ok) flag(a.status, b, EKS_STATUS_SINGULAR);
   if (!p.smooth) return;
-  double *bw = (double *)(a.ws + p.bwd_off) + ((long long)b * p.NC + c) * MR;
-#pragma unroll
-  for (int i = 0; i < R; ++i) {
-    bw[R * R + i] = g[i];
-#pragma unroll
-    for (int k = 0; k < R; ++k) bw[i * R + k] = G[i][k];
-  }
+  F.store((double *)(a.ws + p.bwd_off) + ((long long)b * p.NC + c) * MR);
 }
 
 template <int R>
@@ -373,18 +351,9 @@ __global__ __launch_bounds__(kBlock) void k_rt_c5(SmoothArgs a, ChunkPlan p) {
   const long long s = c * p.L, e = min(TT, s + p.L);
   double *outb = a.out + (long long)b * a.ob;
   for (long long t = e - 1; t >= s; --t) {
-    double f[MR], nx[R];
-#pragma unroll
-    for (int k = 0; k < MR; ++k) f[k] = pl(jdp, t * MR + k, B, b);
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      double sm = f[R * R + i];
-#pragma unroll
-      for (int k = 0; k < R; ++k) sm = fma(f[i * R + k], ms[k], sm);
-      nx[i] = sm;
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) ms[i] = nx[i];
+    Affine<R> f;
+    f.load_at([&](int k) { return pl(jdp, t * MR + k, B, b); });
+    f.apply(ms);
     project_rt<R>(outb + t * a.ot, a.oj, C, off, n, ms);
     if (a.ms) store_vec<R>(a.ms + ((long long)b * TT + t) * R, ms);
   }

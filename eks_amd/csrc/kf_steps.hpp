@@ -461,6 +461,16 @@ struct Elem {
       }
     }
   }
+  // the filtered state N(m, P) of an element that does not depend on the
+  // state before it (Ab = 0: chunk 0's element, or any prefix that holds it)
+  EKS_DEV void state(double (&m)[R], double (&P)[R][R]) const {
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      m[i] = bb[i];
+#pragma unroll
+      for (int j = 0; j < R; ++j) P[i][j] = Cb[i][j];
+    }
+  }
   // strided store / load: component k at p[k * stride]
   EKS_DEV void store(double *p, long long stride) const {
     int k = 0;

@@ -39,6 +39,7 @@
 #include <cstdlib>
 
 #include "../../include/eks_hip.h"
+#include "affine.hpp"
 #include "eks_common.hpp"
 #include "ensemble.hpp"
 #include "handoff.hpp"
@@ -1230,22 +1231,12 @@ __global__ __launch_bounds__(256) void k_c2_fscan_g(SmoothArgs a, ChunkPlan p) {
       store_state<R>(cst + b, B, m, P);  // chunk 0 starts from the prior
       Elem<R> e0;
       e0.load(erow, 1);
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        m[i] = e0.bb[i];
-#pragma unroll
-        for (int j = 0; j < R; ++j) P[i][j] = e0.Cb[i][j];
-      }
+      e0.state(m, P);
       c = 1;
     } else {
       // chunk 0's element is the filtered state itself (Ab = 0), so the
       // prefix is the state entering c0
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        m[i] = ex.bb[i];
-#pragma unroll
-        for (int j = 0; j < R; ++j) P[i][j] = ex.Cb[i][j];
-      }
+      ex.state(m, P);
     }
     double *np_ = (double *)(a.ws + p.nllp_off);
     const bool need = !p.nll_closed;  // the start states feed K3 / K5 (not a closed-form NLL call)
@@ -1286,61 +1277,6 @@ __global__ __launch_bounds__(256) void k_c2_fscan_g(SmoothArgs a, ChunkPlan p) {
   if (!ok) flag(a.status, b, EKS_STATUS_SCAN);
 }
 
-template <int R>
-struct Affine {
-  double G[R][R], g[R];
-  EKS_DEV void set_identity() {
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      g[i] = 0.0;
-#pragma unroll
-      for (int j = 0; j < R; ++j) G[i][j] = (i == j) ? 1.0 : 0.0;
-    }
-  }
-  // (this o h)(x) = G (Gh x + gh) + g
-  EKS_DEV Affine after(const Affine &h) const {
-    Affine o;
-    matmul<R, R, R>(G, h.G, o.G);
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      double t = g[i];
-#pragma unroll
-      for (int k = 0; k < R; ++k) t = fma(G[i][k], h.g[k], t);
-      o.g[i] = t;
-    }
-    return o;
-  }
-  EKS_DEV Affine shfl_down(int delta) const {
-    Affine o;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      o.g[i] = __shfl_down(g[i], delta, 64);
-#pragma unroll
-      for (int j = 0; j < R; ++j) o.G[i][j] = __shfl_down(G[i][j], delta, 64);
-    }
-    return o;
-  }
-};
-
-template <int R>
-EKS_DEV void map_store_wt(const Affine<R> &F, double *p) {
-#pragma unroll
-  for (int i = 0; i < R; ++i) {
-    st_wt(p + R * R + i, F.g[i]);
-#pragma unroll
-    for (int j = 0; j < R; ++j) st_wt(p + i * R + j, F.G[i][j]);
-  }
-}
-template <int R>
-EKS_DEV void map_load_wt(Affine<R> &F, const double *p) {
-#pragma unroll
-  for (int i = 0; i < R; ++i) {
-    F.g[i] = ld_wt(p + R * R + i);
-#pragma unroll
-    for (int j = 0; j < R; ++j) F.G[i][j] = ld_wt(p + i * R + j);
-  }
-}
-
 // K4, chained form: chunk maps ms_start[c] = G_c ms_start[c+1] + g_c, G
 // blocks of 4 waves per trajectory as in K2 but in reverse: the tickets of
 // trajectory b go to its blocks g = G-1 .. 0, and a block waits only for the
@@ -1376,17 +1312,7 @@ __global__ __launch_bounds__(256) void k_c4_bscan_g(SmoothArgs a, ChunkPlan p) {
   const long long cb0 = min(NCb, (long long)g * p.CPB), cb1 = min(NCb, cb0 + p.CPB);
   const long long q = (p.CPB + 255) / 256;
   const long long c0 = min(cb1, cb0 + tid * q), c1 = min(cb1, c0 + q);
-  auto load_map = [&](const double *s) {
-    Affine<R> f;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      f.g[i] = s[R * R + i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) f.G[i][j] = s[i * R + j];
-    }
-    return f;
-  };
-  auto map_of = [&](long long c) { return load_map(bw + (b * NC + c) * MR); };
+  auto map_of = [&](long long c) { return Affine<R>::from(bw + (b * NC + c) * MR); };
   // fn(c, map c) for c = c1-1 down to c0, PD maps in flight (see elem_run)
   auto map_run = [&](auto &&fn) {
     constexpr int PD = 2 * scan_pd<R>();
@@ -1421,29 +1347,24 @@ __global__ __launch_bounds__(256) void k_c4_bscan_g(SmoothArgs a, ChunkPlan p) {
     for (int k = 32; k >= 1; k >>= 1) s += __shfl_xor(s, k, 64);
   }
   if (l == 0) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      tot[w][R * R + i] = F.g[i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) tot[w][i * R + j] = F.G[i][j];
-    }
+    F.store(tot[w]);
     nsum[w] = s;
   }
   __syncthreads();
   Affine<R> S;  // the later waves' totals
   S.set_identity();
   if (w + 1 < W) {
-    S = load_map(tot[W - 1]);
-    for (int v = W - 2; v > w; --v) S = load_map(tot[v]).after(S);
+    S.load(tot[W - 1]);
+    for (int v = W - 2; v > w; --v) S = Affine<R>::from(tot[v]).after(S);
     X = X.after(S);
   }
   double part = nsum[0];  // the block's NLL partial, waves in order
   for (int v = 1; v < W; ++v) part += nsum[v];
   bool ok = true;
   if (w == 0 && g > 0) {  // the block total (and partial), for the earlier blocks
-    const Affine<R> T0 = load_map(tot[0]).after(S);
+    const Affine<R> T0 = Affine<R>::from(tot[0]).after(S);
     if (l == 0) {
-      map_store_wt<R>(T0, maggs + (long long)g * MR);
+      T0.store_wt(maggs + (long long)g * MR);
       st_wt(parts + g, part);
     }
     publish_flag(fl + g, l);
@@ -1454,19 +1375,12 @@ __global__ __launch_bounds__(256) void k_c4_bscan_g(SmoothArgs a, ChunkPlan p) {
       e.set_identity();
       const bool need = l > g && l < G;
       if (!wait_flag_lanes(fl + l, need, a.wait_ticks)) ok = false;
-      if (need) map_load_wt<R>(e, maggs + (long long)l * MR);
+      if (need) e.load_wt(maggs + (long long)l * MR);
       for (int k = 1; k < G - 1 - g; k <<= 1) {  // lane g+1 needs G-1-g lanes
         const Affine<R> o = e.shfl_down(k);
         if (l + k < 64) e = e.after(o);
       }
-      if (l == g + 1) {
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-          bsuf[R * R + i] = e.g[i];
-#pragma unroll
-          for (int j = 0; j < R; ++j) bsuf[i * R + j] = e.G[i][j];
-        }
-      }
+      if (l == g + 1) e.store(bsuf);
       if (a.nll && g == 0 && l == 0) {  // every other block's partial is visible now
         double tsum = part;
         for (int v = 1; v < G; ++v) tsum += ld_wt(parts + v);
@@ -1474,7 +1388,7 @@ __global__ __launch_bounds__(256) void k_c4_bscan_g(SmoothArgs a, ChunkPlan p) {
       }
     }
     __syncthreads();
-    X = X.after(load_map(bsuf));
+    X = X.after(Affine<R>::from(bsuf));
   } else if (a.nll && G == 1 && tid == 0) {
     a.nll[b] = part;
   }
@@ -1482,29 +1396,19 @@ __global__ __launch_bounds__(256) void k_c4_bscan_g(SmoothArgs a, ChunkPlan p) {
   double ms[R];
   // X maps the value entering the last chunk (none for the globally last
   // segment: its map is constant; the next segment's ms otherwise)
+  if (a.seg_in) {
+    load_vec<R>(a.seg_in + b * R, ms);
+    X.apply(ms);
+  } else {
 #pragma unroll
-  for (int i = 0; i < R; ++i) {
-    double t = X.g[i];
-    if (a.seg_in)
-#pragma unroll
-      for (int k = 0; k < R; ++k) t = fma(X.G[i][k], a.seg_in[b * R + k], t);
-    ms[i] = t;
+    for (int i = 0; i < R; ++i) ms[i] = X.g[i];
   }
   map_run([&](long long c, const Affine<R> &f) {
     if (c + 1 < NCb || a.seg_in) {
 #pragma unroll
       for (int i = 0; i < R; ++i) msend[(c * R + i) * B + b] = ms[i];
     }
-    double nx[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      double t = f.g[i];
-#pragma unroll
-      for (int k = 0; k < R; ++k) t = fma(f.G[i][k], ms[k], t);
-      nx[i] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) ms[i] = nx[i];
+    f.apply(ms);
   });
 }
 
@@ -1562,7 +1466,8 @@ __global__ __launch_bounds__(64 * W) void k_seg_elems(SmoothArgs a, ChunkPlan p)
 // maps composed right to left), same block shape as k_seg_elems.
 template <int R, int W>
 __global__ __launch_bounds__(64 * W) void k_seg_maps(SmoothArgs a, ChunkPlan p) {
-  __shared__ double tot[W][R * R + R];
+  constexpr int MR = R * R + R;
+  __shared__ double tot[W][MR];
   const long long b = blockIdx.x;
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
   const long long NC = p.NC;
@@ -1570,42 +1475,19 @@ __global__ __launch_bounds__(64 * W) void k_seg_maps(SmoothArgs a, ChunkPlan p) 
   const double *bw = (const double *)(a.ws + p.bwd_off);
   const long long q = (NC + 64 * W - 1) / (64 * W);
   const long long c0 = min(NC, (long long)tid * q), c1 = min(NC, c0 + q);
-  auto load_map = [&](const double *sp) {
-    Affine<R> f;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      f.g[i] = sp[R * R + i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) f.G[i][j] = sp[i * R + j];
-    }
-    return f;
-  };
   Affine<R> F;
   F.set_identity();
-  for (long long c = c1 - 1; c >= c0; --c) F = load_map(bw + (b * NC + c) * (R * R + R)).after(F);
+  for (long long c = c1 - 1; c >= c0; --c) F = Affine<R>::from(bw + (b * NC + c) * MR).after(F);
 #pragma unroll
   for (int k = 1; k < 64; k <<= 1) {
     const Affine<R> o = F.shfl_down(k);
     if (l + k < 64) F = F.after(o);
   }
-  if (l == 0) {
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      tot[w][R * R + i] = F.g[i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) tot[w][i * R + j] = F.G[i][j];
-    }
-  }
+  if (l == 0) F.store(tot[w]);
   __syncthreads();
   if (tid == 0) {
-    for (int v = 1; v < W; ++v) F = F.after(load_map(tot[v]));
-    double *o = a.seg_out + b * (R * R + R);
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      o[R * R + i] = F.g[i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) o[i * R + j] = F.G[i][j];
-    }
+    for (int v = 1; v < W; ++v) F = F.after(Affine<R>::from(tot[v]));
+    F.store(a.seg_out + b * MR);
   }
 }
 
@@ -1628,12 +1510,7 @@ __global__ __launch_bounds__(64) void k_seg_combine(int kind, long long B, int n
     Elem<R> e0;
     e0.load(in + b * EL, 1);
     double m[R], P[R][R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      m[i] = e0.bb[i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) P[i][j] = e0.Cb[i][j];
-    }
+    e0.state(m, P);
     for (int sg = 1; sg < self; ++sg) {
       Elem<R> e;
       e.load(in + ((long long)sg * B + b) * EL, 1);
@@ -1645,19 +1522,8 @@ __global__ __launch_bounds__(64) void k_seg_combine(int kind, long long B, int n
     double ms[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) ms[i] = 0.0;
-    for (int sg = nseg - 1; sg > self; --sg) {
-      const double *f = in + ((long long)sg * B + b) * ML;
-      double nx[R];
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        double t = f[R * R + i];
-#pragma unroll
-        for (int k = 0; k < R; ++k) t = fma(f[i * R + k], ms[k], t);
-        nx[i] = t;
-      }
-#pragma unroll
-      for (int i = 0; i < R; ++i) ms[i] = nx[i];
-    }
+    for (int sg = nseg - 1; sg > self; --sg)
+      Affine<R>::from(in + ((long long)sg * B + b) * ML).apply(ms);
 #pragma unroll
     for (int i = 0; i < R; ++i) out[b * R + i] = ms[i];
   }
@@ -1701,6 +1567,9 @@ __global__ __launch_bounds__(kBlock) void k_c3_rerun(SmoothArgs a, ChunkPlan p) 
     if (!valid) return;
   }
   constexpr int KS = R + Sym<R>::len, MR = R * R + R;
+  // the chunk's RTS map, as plain arrays with Affine::then / then_const /
+  // store written out: held in an Affine, the 3-latent group-mode
+  // instantiations of this kernel spill (0 -> 10 VGPRs to scratch)
   double G[R][R], g[R];
 #pragma unroll
   for (int i = 0; i < R; ++i) {
@@ -1891,16 +1760,8 @@ __global__ __launch_bounds__(64) void k_c4_bscan(SmoothArgs a, ChunkPlan p) {
   const double *bw = (const double *)(a.ws + p.bwd_off);
   double *msend = (double *)(a.ws + p.msend_off);
   const double *np_ = (const double *)(a.ws + p.nllp_off);
-  auto load_map = [&](long long c, double (&G)[R][R], double (&g)[R]) {
-    const double *q = bw + (b * p.NC + c) * (R * R + R);
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      g[i] = q[R * R + i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) G[i][j] = q[i * R + j];
-    }
-  };
-  double ms[R], G[R][R], g[R], Gn[R][R], gn[R];
+  auto map_of = [&](long long c) { return Affine<R>::from(bw + (b * p.NC + c) * (R * R + R)); };
+  double ms[R];
   // the value entering the last chunk: none for the globally last segment
   // (its map is constant), the next segment's ms otherwise
 #pragma unroll
@@ -1908,27 +1769,14 @@ __global__ __launch_bounds__(64) void k_c4_bscan(SmoothArgs a, ChunkPlan p) {
   if (a.seg_in)
 #pragma unroll
     for (int i = 0; i < R; ++i) msend[((p.NC - 1) * R + i) * B + b] = ms[i];
-  load_map(p.NC - 1, G, g);
+  Affine<R> F = map_of(p.NC - 1), Fn;
   for (long long c = p.NC - 1; c >= 0; --c) {
-    if (c >= 1) load_map(c - 1, Gn, gn);  // next map in flight during this one
-    double nx[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      double s = g[i];
-#pragma unroll
-      for (int j = 0; j < R; ++j) s = fma(G[i][j], ms[j], s);
-      nx[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) ms[i] = nx[i];
+    if (c >= 1) Fn = map_of(c - 1);  // next map in flight during this one
+    F.apply(ms);
     if (c >= 1) {
 #pragma unroll
-      for (int i = 0; i < R; ++i) {
-        msend[((c - 1) * R + i) * B + b] = ms[i];
-        g[i] = gn[i];
-#pragma unroll
-        for (int j = 0; j < R; ++j) G[i][j] = Gn[i][j];
-      }
+      for (int i = 0; i < R; ++i) msend[((c - 1) * R + i) * B + b] = ms[i];
+      F = Fn;
     }
   }
   if (a.nll) {
@@ -1971,23 +1819,16 @@ EKS_DEV void c5_ms_in(const SmoothArgs &a, const ChunkPlan &p, long long c, unsi
     if (c + 1 < p.NC) {
       const long long blk = blockIdx.x;
       const bool last_group = ((p.NC - 1) * B + b) / kBlock == blk;
-      double mg[R];
+      if (!last_group)
 #pragma unroll
-      for (int i = 0; i < R; ++i)
-        mg[i] = last_group ? 0.0 : pl((const double *)(a.ws + p.gms_off), blk * R + i, B, b);
+        for (int i = 0; i < R; ++i) ms[i] = pl((const double *)(a.ws + p.gms_off), blk * R + i, B, b);
       if (threadIdx.x + B < kBlock) {
-        const double *f = (const double *)(a.ws + p.bwd_off) + ((long long)b * p.NC + c + 1) * (R * R + R);
+        const Affine<R> f = Affine<R>::from((const double *)(a.ws + p.bwd_off) +
+                                            ((long long)b * p.NC + c + 1) * (R * R + R));
+        if (!last_group) f.apply(ms);
+        else
 #pragma unroll
-        for (int i = 0; i < R; ++i) {
-          double t = f[R * R + i];
-          if (!last_group)
-#pragma unroll
-            for (int k = 0; k < R; ++k) t = fma(f[i * R + k], mg[k], t);
-          ms[i] = t;
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < R; ++i) ms[i] = mg[i];
+          for (int i = 0; i < R; ++i) ms[i] = f.g[i];
       }
     }
   } else if (c + 1 < p.NC || a.t_base + TT < a.T_total) {
@@ -2030,7 +1871,7 @@ __global__ __launch_bounds__(kBlock) void k_c5_final(SmoothArgs a, ChunkPlan p) 
     // `if` around each would serialise them (see c1_stream)
 #pragma unroll
     for (int j = 0; j < LS; ++j) load_yev<N, YT>(ybuf, evbuf, min(t0 + j, e - 1), p.yB, p.ylane(b), yr[j], er[j]);
-    double Jr[LS][R][R], dr[LS][R];
+    Affine<R> sr[LS];  // the steps' RTS maps (J_t, d_t)
 #pragma unroll
     for (int j = 0; j < LS; ++j) {
       const long long t = t0 + j;
@@ -2044,13 +1885,13 @@ __global__ __launch_bounds__(kBlock) void k_c5_final(SmoothArgs a, ChunkPlan p) 
         if (t + a.t_base > 0) kf_predict<R, AI>(m, P, md.A, md.Q);
         kf_update<R, N, CI>(m, P, md.C, y, rv, dummy, ok);
         if (t + a.t_base + 1 < a.T_total) {
-          ok = rts_gain<R, AI>(m, P, md.A, md.Q, Jr[j], dr[j]) && ok;
+          ok = rts_gain<R, AI>(m, P, md.A, md.Q, sr[j].G, sr[j].g) && ok;
         } else {
 #pragma unroll
           for (int i = 0; i < R; ++i) {
-            dr[j][i] = m[i];
+            sr[j].g[i] = m[i];
 #pragma unroll
-            for (int q = 0; q < R; ++q) Jr[j][i][q] = 0.0;
+            for (int q = 0; q < R; ++q) sr[j].G[i][q] = 0.0;
           }
         }
       }
@@ -2059,16 +1900,7 @@ __global__ __launch_bounds__(kBlock) void k_c5_final(SmoothArgs a, ChunkPlan p) 
     for (int j = LS - 1; j >= 0; --j) {
       const long long t = t0 + j;
       if (t < e) {
-        double nx[R];
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-          double sm = dr[j][i];
-#pragma unroll
-          for (int q = 0; q < R; ++q) sm = fma(Jr[j][i][q], ms[q], sm);
-          nx[i] = sm;
-        }
-#pragma unroll
-        for (int i = 0; i < R; ++i) ms[i] = nx[i];
+        sr[j].apply(ms);
         project_store<R, N, CI>(outb + t * a.ot, a.oj, md.C, ms, md.off);
         if (a.ms) store_vec<R>(a.ms + ((long long)b * TT + t) * R, ms);
       }
@@ -2128,6 +1960,9 @@ __global__ __launch_bounds__(kBlock) void k_c5_jd(SmoothArgs a, ChunkPlan p) {
   }
 }
 
+// algo 3 (its plan, kernels and launcher), inside this namespace
+#include "two_pass.hpp"
+
 // ===========================================================================
 // host launcher for one (R, N, AI, CI)
 // ===========================================================================
@@ -2140,8 +1975,6 @@ int dispatch_members_c(int E, F &&f) {
     default: return f(ic<0>{});
   }
 }
-
-#include "two_pass.hpp"
 
 template <int R, int N, int AI, int CI>
 int launch_shape(const SmoothArgs &a, int algo, long long L) {

@@ -42,22 +42,6 @@ constexpr int kK3BD = EKS_K3B_D;
 #endif
 constexpr int kK3YevD = EKS_K3_YEV_D;
 
-// algo 3's chains: every unit publishes its aggregate (k3_fwd: its element,
-// k3_bwd: its map) as soon as it has it, before looking at its neighbour, so
-// a later unit never waits for an earlier one's own chain wait -- only for
-// its stream to end (0: only a unit that finds its neighbour not ready
-// publishes one, round 4's rule)
-#ifndef EKS_EAGER_AGG
-#define EKS_EAGER_AGG 0
-#endif
-constexpr bool kEagerAgg = EKS_EAGER_AGG != 0;
-// k3_bwd's look-back instantiation for every batch of the single-view shape
-// (0: only for batches of at most kLbGroups groups, round 4's rule)
-#ifndef EKS_A3_LB_ALL
-#define EKS_A3_LB_ALL 0
-#endif
-constexpr bool kLbAll = EKS_A3_LB_ALL != 0;
-
 // algo 3's chains: wave 0 issues the poll of its neighbour's flag as soon as
 // its own stream ends (before the unit's element / map composition and its
 // barrier), and uses the word at the chain point when it already says

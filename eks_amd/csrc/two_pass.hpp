@@ -310,50 +310,6 @@ EKS_DEV void state_store_pl_wt(double *base, long long plane0, long long B, unsi
 #pragma unroll
     for (int j = i; j < R; ++j) st_wt(&pl(base, plane0 + (k++), B, b), P[i][j]);
 }
-// ms <- G ms + g (the one expression every application of a chunk map uses,
-// so that a mean carried through any number of maps has the same bits
-// whichever unit applies them)
-template <int R>
-EKS_DEV void apply_map(const double (&G)[R][R], const double (&g)[R], double (&ms)[R]) {
-  double nx[R];
-#pragma unroll
-  for (int u = 0; u < R; ++u) {
-    double sm = g[u];
-#pragma unroll
-    for (int q = 0; q < R; ++q) sm = fma(G[u][q], ms[q], sm);
-    nx[u] = sm;
-  }
-#pragma unroll
-  for (int u = 0; u < R; ++u) ms[u] = nx[u];
-}
-
-// H <- F o H for affine maps (F applied after H): G = F.G H.G, g = F.G H.g + F.g
-template <int R>
-EKS_DEV void compose_map(const double (&FG)[R][R], const double (&Fg)[R], double (&HG)[R][R],
-                         double (&Hg)[R]) {
-  double G[R][R], g[R];
-#pragma unroll
-  for (int u = 0; u < R; ++u) {
-#pragma unroll
-    for (int v = 0; v < R; ++v) {
-      double t = 0.0;
-#pragma unroll
-      for (int q = 0; q < R; ++q) t = fma(FG[u][q], HG[q][v], t);
-      G[u][v] = t;
-    }
-    double t = Fg[u];
-#pragma unroll
-    for (int q = 0; q < R; ++q) t = fma(FG[u][q], Hg[q], t);
-    g[u] = t;
-  }
-#pragma unroll
-  for (int u = 0; u < R; ++u) {
-    Hg[u] = g[u];
-#pragma unroll
-    for (int v = 0; v < R; ++v) HG[u][v] = G[u][v];
-  }
-}
-
 // The first D steps of a lane's chunk into the ring (issued ahead: for the
 // next unit while the current one finishes its tail).
 template <int D, typename Src>
@@ -668,15 +624,7 @@ EKS_DEV unsigned k3_fwd_run(const SmoothArgs &a, const Plan3 &p, const Sched3 &s
         const unsigned *fl = flags + grp * p.NCu;  // group-major: a walk reads consecutive words
         long long j = cu - 1;
         const bool agg = cu + 1 < p.NCu;  // (the last unit has no successor)
-        if (kEagerAgg) {
-          // the aggregate's stores go out with the neighbour's poll (the poll's
-          // wait covers them), then its flag: later units fold it instead of
-          // waiting for this unit's own chain wait
-          if (agg && lane_ok) elem_store_pl_wt<R>(Ec, agg1, cu * EL, B, b);
-          const bool ready = inc_ready(fl + j, a.wait_ticks);
-          if (agg) publish_flag(flags + grp * p.NCu + cu, l, kAggReady);
-          if (!ready) j = look_back(fl, j, 1, -1, p.NCu, a.wait_ticks, ok);
-        } else if (!(kEarlyPoll && inc_ready_early(early, a.wait_ticks)) &&
+        if (!(kEarlyPoll && inc_ready_early(early, a.wait_ticks)) &&
                    !inc_ready(fl + j, a.wait_ticks)) {
           if (agg) {
             if (lane_ok) elem_store_pl_wt<R>(Ec, agg1, cu * EL, B, b);
@@ -905,30 +853,13 @@ EKS_DEV unsigned k3_bwd_run(const SmoothArgs &a, const Plan3 &p, const Sched3 &s
               for (int v = 0; v < R; ++v) Jr[ir][u][v] = J[u][v];
             }
           }
-          Affine<R> step;
-#pragma unroll
-          for (int u = 0; u < R; ++u) {
-            step.g[u] = d[u];
-#pragma unroll
-            for (int v = 0; v < R; ++v) step.G[u][v] = J[u][v];
-          }
-          Mp = Mp.after(step);
+          Mp.then(J, d);
         } else {
           if (i >= NL) {
 #pragma unroll
             for (int u = 0; u < R; ++u) dr[ir][u] = m[u];
           }
-#pragma unroll
-          for (int u = 0; u < R; ++u) {
-            double sg = Mp.g[u];
-#pragma unroll
-            for (int v = 0; v < R; ++v) sg = fma(Mp.G[u][v], m[v], sg);
-            Mp.g[u] = sg;
-          }
-#pragma unroll
-          for (int u = 0; u < R; ++u)
-#pragma unroll
-            for (int v = 0; v < R; ++v) Mp.G[u][v] = 0.0;
+          Mp.then_const(m);
         }
       };
       if (full) {
@@ -958,6 +889,10 @@ EKS_DEV unsigned k3_bwd_run(const SmoothArgs &a, const Plan3 &p, const Sched3 &s
     // wave 0: the next unit's flag polled now, read at the chain point
     unsigned early = 0u;
     if (kEarlyPoll && w == 0 && cc + 1 < p.NCc) early = ld_flag(flags + grp * p.NCc + cc + 1);
+    // (the maps' LDS-plane and agg2-plane loads and stores below are written
+    // out, not Affine::load_at / store_at: this kernel runs at its register
+    // limit, and the members' element order changes the register allocation
+    // of every instantiation)
     if (w >= 1) {
       int k = 0;
 #pragma unroll
@@ -980,56 +915,48 @@ EKS_DEV unsigned k3_bwd_run(const SmoothArgs &a, const Plan3 &p, const Sched3 &s
       // this unit publishes U for the units before it, walks forward to the
       // nearest unit j with a published mean and carries that mean back
       // through the maps U of units j-1 .. cc+1 with the expression every
-      // unit uses (apply_map): the same bits whichever j it starts from.
+      // unit uses (Affine::apply): the same bits whichever j it starts from.
       // The walk's loads go out KLB units at a time (one round trip per KLB
       // units instead of one per chunk map).
       constexpr int KLB = 4;
-      double UG[R][R], Ug[R];
+      Affine<R> U;
 #pragma unroll
       for (int u = 0; u < R; ++u) {
-        Ug[u] = shM[kWV - 2][R * R + u][l];
+        U.g[u] = shM[kWV - 2][R * R + u][l];
 #pragma unroll
-        for (int v = 0; v < R; ++v) UG[u][v] = shM[kWV - 2][u * R + v][l];
+        for (int v = 0; v < R; ++v) U.G[u][v] = shM[kWV - 2][u * R + v][l];
       }
 #pragma unroll
       for (int v = kWV - 2; v >= 1; --v) {
-        double G[R][R], g[R];
+        Affine<R> Mv;
 #pragma unroll
         for (int u = 0; u < R; ++u) {
-          g[u] = shM[v - 1][R * R + u][l];
+          Mv.g[u] = shM[v - 1][R * R + u][l];
 #pragma unroll
-          for (int q = 0; q < R; ++q) G[u][q] = shM[v - 1][u * R + q][l];
+          for (int q = 0; q < R; ++q) Mv.G[u][q] = shM[v - 1][u * R + q][l];
         }
-        compose_map<R>(G, g, UG, Ug);
+        U = Mv.after_by_rows(U);
       }
-      compose_map<R>(Mp.G, Mp.g, UG, Ug);
+      U = Mp.after_by_rows(U);
 #pragma unroll
       for (int u = 0; u < R; ++u) ms[u] = 0.0;
       if (cc + 1 < p.NCc) {
         const unsigned *fl = flags + grp * p.NCc;  // group-major
         long long j = cc + 1;
-        auto store_agg = [&]() {
-          if (lane_ok) {
-#pragma unroll
-            for (int u = 0; u < R; ++u) {
-#pragma unroll
-              for (int q = 0; q < R; ++q) st_wt(&pl(agg2, cc * MP + u * R + q, B, b), UG[u][q]);
-              st_wt(&pl(agg2, cc * MP + R * R + u, B, b), Ug[u]);
-            }
-          }
-        };
         const bool early_ok = kEarlyPoll && inc_ready_early(early, a.wait_ticks);
         if (!LB) {
           if (!early_ok && !wait_flag(fl + j, a.wait_ticks, kIncReady)) okc = false;
         } else if (early_ok) {
-        } else if (kEagerAgg) {  // (as k3_fwd: U published with the poll)
-          if (cc > 0) store_agg();
-          const bool ready = inc_ready(fl + j, a.wait_ticks);
-          if (cc > 0) publish_flag(flags + grp * p.NCc + cc, l, kAggReady);
-          if (!ready) j = look_back(fl, j, 1, +1, p.NCc, a.wait_ticks, okc);
         } else if (!inc_ready(fl + j, a.wait_ticks)) {
           if (cc > 0) {
-            store_agg();
+            if (lane_ok) {
+#pragma unroll
+              for (int u = 0; u < R; ++u) {
+#pragma unroll
+                for (int q = 0; q < R; ++q) st_wt(&pl(agg2, cc * MP + u * R + q, B, b), U.G[u][q]);
+                st_wt(&pl(agg2, cc * MP + R * R + u, B, b), U.g[u]);
+              }
+            }
             publish_flag(flags + grp * p.NCc + cc, l, kAggReady);
           }
           j = look_back(fl, j, 1, +1, p.NCc, a.wait_ticks, okc);
@@ -1040,20 +967,20 @@ EKS_DEV unsigned k3_bwd_run(const SmoothArgs &a, const Plan3 &p, const Sched3 &s
 #pragma unroll
           for (int u = 0; u < R; ++u) ms[u] = ld_wt(&pl(inc, j * R + u, B, b));
           for (long long i0 = j - 1; i0 > cc; i0 -= KLB) {
-            double G[KLB][R][R], g[KLB][R];
+            Affine<R> Ui[KLB];
 #pragma unroll
             for (int k = 0; k < KLB; ++k) {
               const long long i = i0 - k > cc ? i0 - k : i0;  // (past cc: a re-load, unused)
 #pragma unroll
               for (int u = 0; u < R; ++u) {
 #pragma unroll
-                for (int q = 0; q < R; ++q) G[k][u][q] = ld_wt(&pl(agg2, i * MP + u * R + q, B, b));
-                g[k][u] = ld_wt(&pl(agg2, i * MP + R * R + u, B, b));
+                for (int q = 0; q < R; ++q) Ui[k].G[u][q] = ld_wt(&pl(agg2, i * MP + u * R + q, B, b));
+                Ui[k].g[u] = ld_wt(&pl(agg2, i * MP + R * R + u, B, b));
               }
             }
 #pragma unroll
             for (int k = 0; k < KLB; ++k)
-              if (i0 - k > cc) apply_map<R>(G[k], g[k], ms);
+              if (i0 - k > cc) Ui[k].apply(ms);
           }
         }
       }
@@ -1063,20 +990,20 @@ EKS_DEV unsigned k3_bwd_run(const SmoothArgs &a, const Plan3 &p, const Sched3 &s
       for (int u = 0; u < R; ++u) mnext[u] = ms[u];
 #pragma unroll
       for (int v = kWV - 1; v >= 1; --v) {
-        double G[R][R], g[R];
+        Affine<R> Mv;
         int k = 0;
 #pragma unroll
         for (int u = 0; u < R; ++u)
 #pragma unroll
-          for (int q = 0; q < R; ++q) G[u][q] = shM[v - 1][k++][l];
+          for (int q = 0; q < R; ++q) Mv.G[u][q] = shM[v - 1][k++][l];
 #pragma unroll
-        for (int u = 0; u < R; ++u) g[u] = shM[v - 1][k++][l];
+        for (int u = 0; u < R; ++u) Mv.g[u] = shM[v - 1][k++][l];
 #pragma unroll
         for (int u = 0; u < R; ++u) shM[v - 1][u][l] = ms[u];
-        apply_map<R>(G, g, ms);
+        Mv.apply(ms);
       }
       if (cc > 0) {  // the mean at this coarse chunk's first step: U(mean entering the unit)
-        apply_map<R>(UG, Ug, mnext);
+        U.apply(mnext);
         if (lane_ok)
 #pragma unroll
           for (int u = 0; u < R; ++u) st_wt(&pl(inc, cc * R + u, B, b), mnext[u]);
@@ -1135,17 +1062,9 @@ EKS_DEV unsigned k3_bwd_run(const SmoothArgs &a, const Plan3 &p, const Sched3 &s
           for (int i = 0; i < R; ++i) ms[i] = mf[i];
           return;
         }
-        double J[R][R], d[R], nx[R];
-        ok = rts_gain<R, AI>(mf, Pf, md.A, md.Q, J, d) && ok;
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-          double sm = d[i];
-#pragma unroll
-          for (int u = 0; u < R; ++u) sm = fma(J[i][u], ms[u], sm);
-          nx[i] = sm;
-        }
-#pragma unroll
-        for (int i = 0; i < R; ++i) ms[i] = nx[i];
+        Affine<R> jd;  // (J_t, d_t)
+        ok = rts_gain<R, AI>(mf, Pf, md.A, md.Q, jd.G, jd.g) && ok;
+        jd.apply(ms);
       };
       // the last NR steps from registers, then the first NL from LDS
       auto bwd_reg = [&](const int i, const long long tt, auto fullc) {
@@ -1236,7 +1155,7 @@ constexpr long long kLbGroups = 48;
 inline bool a3_bwd_lookback(const Plan3 &p) {
   if (g_a3_lb == 1) return false;
   if (g_a3_lb == 2) return true;
-  return kLbAll || p.ng <= kLbGroups;
+  return p.ng <= kLbGroups;
 }
 
 // host: the launches of one algo-3 call
