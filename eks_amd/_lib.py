@@ -26,6 +26,12 @@ EKS_MEDIAN, EKS_MEAN = 0, 1
 EKS_DBG_WAIT_US, EKS_DBG_A3_SLICE_BYTES, EKS_DBG_FIT_SELECT, EKS_DBG_A3_MODE = 1, 2, 3, 4
 EKS_DBG_A3_LB = 5
 EKS_DBG_RT_FORM = 6
+# eks_smooth_plan_info: index of every value (EKS_PLAN_* in the header), and their names
+(EKS_PLAN_ALGO, EKS_PLAN_L, EKS_PLAN_NC, EKS_PLAN_LS, EKS_PLAN_UNIFORM, EKS_PLAN_WAVE_SCAN,
+ EKS_PLAN_GRP, EKS_PLAN_JD, EKS_PLAN_G, EKS_PLAN_NG, EKS_PLAN_FINE_LEN, EKS_PLAN_NCF,
+ EKS_PLAN_NCC, EKS_PLAN_NCU, EKS_PLAN_NGRP3, EKS_PLAN_INFO_LEN) = range(16)
+PLAN_FIELDS = ("algo", "L", "NC", "LS", "uniform_lanes", "wave_scan", "grp", "jd", "G", "NG",
+               "fine_len3", "NCf", "NCc", "NCu", "ng")
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -51,6 +57,7 @@ SIGNATURES = {
                           _p, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _i32, _i32, _p, _p]),
     "eks_smooth_chunk_len": (_i64, [_i64, _i64, _i32]),
     "eks_smooth_algo": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "eks_smooth_plan_info": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, _i32, _p, _i32]),
     "eks_smooth_seg_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "eks_smooth_seg": (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
                               _i32, _p, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _i32, _p, _i64,
@@ -72,6 +79,20 @@ SIGNATURES = {
     "eks_csv_read": (_i32, [C.c_char_p, _i32, _p, _i64, _i64, _p, _p, _i64, _i32]),
     "eks_profile_end": (_i32, [_p, _p, _i32, _i32]),
 }
+
+
+def plan_info(B: int, T: int, n: int, r: int, E: int, algo: int, smoothing: bool = True) -> dict:
+    """eks_smooth_plan_info as a dict keyed by PLAN_FIELDS (host only: no GPU
+    needed); only the fields the resolved algo defines are present."""
+    buf = (C.c_int64 * EKS_PLAN_INFO_LEN)()
+    k = load().eks_smooth_plan_info(B, T, n, r, E, algo, 1 if smoothing else 0, buf,
+                                    EKS_PLAN_INFO_LEN)
+    if k <= 0:
+        raise EksError(f"eks_smooth_plan_info: no plan for B={B} T={T} n={n} r={r} algo={algo}")
+    info = {name: int(buf[i]) for i, name in enumerate(PLAN_FIELDS) if i < k}
+    if info["algo"] == 3:  # algo 3 has no chunk plan: its own fields only
+        info = {name: v for name, v in info.items() if name == "algo" or name in PLAN_FIELDS[10:]}
+    return info
 
 
 def debug_set(key: int, value: int) -> int:

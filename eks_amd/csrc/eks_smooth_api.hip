@@ -1,7 +1,7 @@
 // C ABI of the fused smoother: eks_smooth, eks_smooth_workspace_bytes,
-// eks_smooth_chunk_len (include/eks_hip.h).  Validates arguments, zeroes the
-// status array, picks the algorithm and dispatches to the per-shape
-// launchers of eks_shape_*.hip.
+// eks_smooth_chunk_len, eks_smooth_plan_info (include/eks_hip.h).  Validates
+// arguments, zeroes the status array, picks the algorithm and dispatches to
+// the per-shape launchers of eks_shape_*.hip.
 #include "smooth_impl.hpp"
 
 using namespace eks;
@@ -59,6 +59,48 @@ int eks_smooth_algo(int64_t B, int64_t T, int n, int r, int E, int algo) {
   if (B <= 0 || T <= 0 || r < 1 || n < 1 || algo < 0 || algo > 4) return 0;
   if (use_rt(r, n, algo)) return 4;
   return pick_algo(B, T, n, r, E, algo);
+}
+
+int eks_smooth_plan_info(int64_t B, int64_t T, int n, int r, int E, int algo, int smoothing,
+                         int64_t *info, int n_info) {
+  if (B <= 0 || T <= 0 || r < 1 || n < 1 || algo < 0 || algo > 4 || !info || n_info < 0) return 0;
+  int64_t v[EKS_PLAN_INFO_LEN] = {0};
+  int len = 0;
+  if (use_rt(r, n, algo)) {
+    v[EKS_PLAN_ALGO] = 4;  // the runtime-n kernels plan for themselves (eks_shape_rt.hip)
+    len = 1;
+  } else if (!shape_compiled(r, n)) {
+    return 0;
+  } else {
+    int al = pick_algo(B, T, n, r, E, algo);
+    if (al == 3 && !smoothing) al = 2;  // as smooth_call: algo 3 has no filter-only mode
+    v[EKS_PLAN_ALGO] = al;
+    len = 1;
+    if (al == 2) {
+      const ChunkPlan p = make_plan(B, T, r, n, call_chunk_len(B, T, r, smoothing != 0, 0));
+      const ChunkForm f = chunk_form(p, B, smoothing != 0, 0);
+      v[EKS_PLAN_L] = p.L;
+      v[EKS_PLAN_NC] = p.NC;
+      v[EKS_PLAN_LS] = p.LS;
+      v[EKS_PLAN_UNIFORM] = f.uni;
+      v[EKS_PLAN_WAVE_SCAN] = f.wave_scan;
+      v[EKS_PLAN_GRP] = f.grp;
+      v[EKS_PLAN_JD] = f.jd;
+      v[EKS_PLAN_G] = !f.wave_scan ? 1 : f.grp ? p.GG : p.G;
+      v[EKS_PLAN_NG] = f.grp ? p.NG : 0;
+      len = EKS_PLAN_NG + 1;
+    } else if (al == 3) {
+      const Plan3 p = make_plan3(B, T, r, n);
+      v[EKS_PLAN_FINE_LEN] = p.L;
+      v[EKS_PLAN_NCF] = p.NCf;
+      v[EKS_PLAN_NCC] = p.NCc;
+      v[EKS_PLAN_NCU] = p.NCu;
+      v[EKS_PLAN_NGRP3] = p.ng;
+      len = EKS_PLAN_INFO_LEN;
+    }
+  }
+  for (int i = 0; i < len && i < n_info; ++i) info[i] = v[i];
+  return len;
 }
 
 size_t eks_smooth_workspace_bytes(int64_t B, int64_t T, int n, int r, int E, int algo) {
@@ -127,8 +169,7 @@ static int smooth_call(const void *obs, int obs_dtype, int64_t B, int64_t T, int
   a.seg_out = seg_out;
   a.wait_ticks = g_wait_ticks;
   if (rt) return launch_rt(a);  // model_flags are promises only: the general kernel serves all
-  long long L = (out && phase == 0) ? chunk_len_smooth(B, T, r) : chunk_len(B, T, r);
-  if (L >= T) L = (T + 7) / 8 * 8;
+  const long long L = call_chunk_len(B, T, r, out != nullptr, phase);
   if (r == 2 && n == 2) return launch_22(a, al, L);
   if (n == 4) return launch_34(a, al, L);
   if (n == 6) return launch_36(a, al, L);

@@ -197,6 +197,14 @@ inline long long chunk_len_smooth(long long B, long long T, int r) {
   return (T + Ls - 1) / Ls > wave_scan_chunks() ? Ls : L;
 }
 
+// Chunk length handed to the launcher of one call (smooth: out != NULL;
+// phase 0: the whole pipeline); a single chunk is rounded up to the
+// checkpoint grid
+inline long long call_chunk_len(long long B, long long T, int r, bool smooth, int phase) {
+  const long long L = (smooth && phase == 0) ? chunk_len_smooth(B, T, r) : chunk_len(B, T, r);
+  return L >= T ? (T + 7) / 8 * 8 : L;
+}
+
 struct ChunkPlan {
   long long L = 0, NC = 0, NSUB = 0;
   int LS = 8;
@@ -580,6 +588,30 @@ struct Lane {
 inline bool uniform_lanes(long long B) {
   const long long cap = blocks_per_chunk(B) * kBlock;
   return (cap - B) * 8 <= cap;  // at most 1/8 of the lanes idle
+}
+
+// The kernel forms of one algo-2 call, decided here only: launch_shape runs
+// them and eks_smooth_plan_info reports them.
+struct ChunkForm {
+  bool uni = false;        // the U = true instantiations of K1 / K3 / K5
+  bool wave_scan = false;  // k_c2_fscan_g / k_c4_bscan_g, else the serial chunk scans
+  bool grp = false;        // group mode (ChunkPlan::grp)
+  bool jd = false;         // k_c5_jd in place of k_c5_final (ChunkPlan::jd)
+};
+
+// p: make_plan's plan of the call; smooth: out != NULL; phase: 0 = the whole
+// pipeline, 1..3 = a time segment's phases
+inline ChunkForm chunk_form(const ChunkPlan &p, long long B, bool smooth, int phase) {
+  ChunkForm f;
+  f.uni = uniform_lanes(B);
+  // one lane per trajectory while the chain is short, one wave per
+  // trajectory (log-depth scan) when it is long
+  f.wave_scan = p.NC > wave_scan_chunks();
+  // group mode: few trajectories, smoothing, whole pipeline, chained scans
+  // (B <= 256: every block but the last holds chunks of every trajectory)
+  f.grp = !f.uni && B <= kBlock && smooth && phase == 0 && f.wave_scan && p.NG > 0;
+  f.jd = p.jd_off != 0 && smooth && phase == 0;
+  return f;
 }
 
 // element `plane` of a time-major plane array (B values per plane): uniform
@@ -2016,14 +2048,12 @@ int launch_shape(const SmoothArgs &a, int algo, long long L) {
   p.yB = shared ? 1 : a.B;
   // (int step indices in the scalar path: T < 2^31 / N)
   p.ywave = (shared && (uniform_lanes(a.B) || a.B % 64 == 0) && a.T * N < (1LL << 31)) ? 1 : 0;
-  const bool uni = uniform_lanes(a.B);
-  // group mode: few trajectories, smoothing, whole pipeline, chained scans
-  // (B <= 256: every block but the last holds chunks of every trajectory)
-  p.grp = (!uni && a.B <= kBlock && p.smooth && a.phase == 0 && p.NC > wave_scan_chunks() &&
-           p.NG > 0) ? 1 : 0;
+  const ChunkForm form = chunk_form(p, a.B, p.smooth != 0, a.phase);
+  const bool uni = form.uni;
+  p.grp = form.grp ? 1 : 0;
   const size_t lds1 = p.grp ? (size_t)Elem<R>::len * kBlock * 8 : 0;  // K1's group scan
   const size_t lds3 = p.grp ? (size_t)(R * R + R + 1) * kBlock * 8 : 0;  // K3's
-  p.jd = (p.jd_off && p.smooth && a.phase == 0) ? 1 : 0;
+  p.jd = form.jd ? 1 : 0;
   ChunkPlan pg = p, p4 = p;  // K2 / K4 over the group totals
   if (p.grp) {
     pg.NC = p4.NC = p.NG;
@@ -2086,9 +2116,8 @@ int launch_shape(const SmoothArgs &a, int algo, long long L) {
         return check_launch("k_seg_elems");
       }
     }
-    // the chunk scans: one lane per trajectory while the chain is short, one
-    // wave per trajectory (log-depth scan) when it is long
-    const bool wave_scan = p.NC > wave_scan_chunks();
+    // the chunk scans: serial or wave-parallel (chunk_form)
+    const bool wave_scan = form.wave_scan;
     const int sw = scan_waves(p.NC);
     // the chained scans' sync words: zeroed by K1 in a whole-pipeline call
     auto zero_sync = [&]() -> int {

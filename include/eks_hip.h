@@ -205,6 +205,42 @@ int64_t eks_smooth_chunk_len(int64_t B, int64_t T, int r);
  * for the bench line and tests. */
 int eks_smooth_algo(int64_t B, int64_t T, int n, int r, int E, int algo);
 
+/* Tests and DESIGN.md: the kernel forms an eks_smooth call of this size takes.
+ * Host only, launches nothing.  Fills up to n_info int64 values, returns how many it defines.
+ * The values come from the launcher's own plan functions, in this order:
+ *   EKS_PLAN_ALGO       the algorithm the call runs (as eks_smooth_algo; a filter-only
+ *                       call that resolves to 3 runs 2).  Algos 1 and 4 define only this.
+ *   algo 2 (the three-pass chunked scan) defines the next nine:
+ *   EKS_PLAN_L          chunk length in steps (a smoothing call of few trajectories
+ *                       uses shorter chunks than a filter-only one)
+ *   EKS_PLAN_NC         chunks per trajectory, ceil(T / L)
+ *   EKS_PLAN_LS         checkpoint interval of K3 / K5 within a chunk
+ *   EKS_PLAN_UNIFORM    1: whole 256-lane blocks per chunk (the uniform-lane kernels)
+ *   EKS_PLAN_WAVE_SCAN  1: the wave-parallel chunk scans, 0: the serial ones
+ *   EKS_PLAN_GRP        1: group mode (in-block scans in K1 / K3, K2 / K4 over groups)
+ *   EKS_PLAN_JD         1: K3 stores the (J, d) planes and k_c5_jd reads them
+ *   EKS_PLAN_G          blocks per trajectory of the chunk scans as launched
+ *                       (over the groups in group mode; 1 for the serial scans)
+ *   EKS_PLAN_NG         groups per trajectory in group mode, else 0
+ *   algo 3 (two passes) leaves those nine 0 and defines:
+ *   EKS_PLAN_FINE_LEN   fine chunk length in steps
+ *   EKS_PLAN_NCF        fine chunks per trajectory
+ *   EKS_PLAN_NCC        units of the backward pass (4 fine chunks each)
+ *   EKS_PLAN_NCU        units of the forward pass (4 fine chunks; 8 at r = 2)
+ *   EKS_PLAN_NGRP3      64-trajectory groups
+ * `smoothing` is nonzero for a call with out != NULL.  Returns 0 for
+ * non-positive sizes, an unknown algo or a shape without kernels.  (eks_smooth
+ * runs algo 2 in place of 3 when the member strides do not fit algo 3's
+ * 32-bit offsets; the query does not see strides.) */
+enum {
+  EKS_PLAN_ALGO = 0, EKS_PLAN_L = 1, EKS_PLAN_NC = 2, EKS_PLAN_LS = 3, EKS_PLAN_UNIFORM = 4,
+  EKS_PLAN_WAVE_SCAN = 5, EKS_PLAN_GRP = 6, EKS_PLAN_JD = 7, EKS_PLAN_G = 8, EKS_PLAN_NG = 9,
+  EKS_PLAN_FINE_LEN = 10, EKS_PLAN_NCF = 11, EKS_PLAN_NCC = 12, EKS_PLAN_NCU = 13,
+  EKS_PLAN_NGRP3 = 14, EKS_PLAN_INFO_LEN = 15
+};
+int eks_smooth_plan_info(int64_t B, int64_t T, int n, int r, int E, int algo,
+                         int smoothing /* out != NULL */, int64_t *info, int n_info);
+
 /*
  * Time-sharded smoothing (SURVEY.md §8(e) "shard the time axis"): the frames
  * of every trajectory are split into nseg contiguous segments, segment k on

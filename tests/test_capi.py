@@ -29,6 +29,37 @@ def test_limits_and_sizes():
     L = lib.eks_smooth_chunk_len(17, 100000, 2)
     assert 16 <= L < 100000 and L % 8 == 0
     assert lib.eks_smooth_chunk_len(1 << 20, 1000, 2) == 0  # enough trajectories: sequential
+    # the kernel forms of a call (eks_smooth_plan_info, host only).  Config 3
+    # (17 x 50 000, r = 3, n = 8): group mode with (J, d) planes, 16-step chunks
+    p = _lib.plan_info(17, 50000, 8, 3, 5, 0)
+    assert p["algo"] == 2 and p["L"] == 16 and p["NC"] == 3125 and p["LS"] == 2
+    assert (p["uniform_lanes"], p["wave_scan"], p["grp"], p["jd"]) == (0, 1, 1, 1)
+    assert p["NG"] == (3125 * 17 + 255) // 256 and p["G"] >= 1
+    # ... its filter-only call keeps eks_smooth_chunk_len's chunks and has no groups
+    f = _lib.plan_info(17, 50000, 8, 3, 5, 0, smoothing=False)
+    assert f["L"] == lib.eks_smooth_chunk_len(17, 50000, 3) and (f["grp"], f["jd"], f["NG"]) == (0, 0, 0)
+    # config 2 (17 x 100 000 single-view): group mode, no (J, d) kernels at r = 2
+    p = _lib.plan_info(17, 100000, 2, 2, 5, 2)
+    assert (p["L"], p["LS"], p["grp"], p["jd"]) == (16, 8, 1, 0)
+    # whole 256-lane blocks per chunk: the uniform-lane kernels, no groups
+    p = _lib.plan_info(256, 100000, 8, 3, 5, 2)
+    assert (p["uniform_lanes"], p["wave_scan"], p["grp"], p["jd"]) == (1, 1, 0, 0)
+    # few chunks: the serial chunk scans
+    p = _lib.plan_info(5, 131, 8, 3, 5, 2)
+    assert (p["NC"], p["wave_scan"], p["grp"], p["G"]) == (9, 0, 0, 1)
+    # algo 3's fine chunks and units; a filter-only call of it runs algo 2
+    p = _lib.plan_info(17408, 10000, 2, 2, 5, 0)
+    assert p["algo"] == 3 and set(p) == {"algo", "fine_len3", "NCf", "NCc", "NCu", "ng"}
+    assert p["NCf"] == -(-10000 // p["fine_len3"]) and p["NCc"] == -(-p["NCf"] // 4)
+    assert p["NCu"] == -(-p["NCf"] // 8) and p["ng"] == 17408 // 64
+    assert _lib.plan_info(17408, 10000, 2, 2, 5, 0, smoothing=False)["algo"] == 2
+    # algos 1 and 4 define the algo alone; sizes eks_smooth rejects define nothing
+    assert _lib.plan_info(1 << 20, 1000, 2, 2, 5, 0) == {"algo": 1}
+    assert _lib.plan_info(17, 50000, 10, 3, 5, 0) == {"algo": 4}
+    buf = (ctypes.c_int64 * 4)(7, 7, 7, 7)
+    assert lib.eks_smooth_plan_info(0, 100, 2, 2, 5, 0, 1, buf, 4) == 0
+    assert lib.eks_smooth_plan_info(17, 50000, 8, 3, 5, 0, 1, buf, 2) == 10  # defined; 2 written
+    assert list(buf) == [2, 16, 7, 7]
     # automatic algorithm: two-pass for many single-view trajectories, the
     # three-pass scan for few or multi-view ones, sequential for very many
     assert lib.eks_smooth_algo(17408, 10000, 2, 2, 5, 0) == 3
