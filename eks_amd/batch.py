@@ -104,13 +104,117 @@ def model_flags(A, C, Q=None) -> int:
     return f
 
 
+def _obs_code(obs, n: int):
+    """(B, T, E, input code) of a member view or a Yev hand-off."""
+    import torch
+    if not isinstance(obs, Yev) and obs.dim() != 4:
+        raise ValueError("obs must be viewed as (B, T, E, n)")
+    B, T, E, nn = obs.shape
+    if nn != n:
+        raise ValueError(f"obs has {nn} coordinates, expected n={n}")
+    if isinstance(obs, Yev):
+        return B, T, E, obs.code
+    if obs.dtype == torch.float32:
+        return B, T, E, _lib.EKS_F32
+    if obs.dtype == torch.float64:
+        return B, T, E, _lib.EKS_F64
+    raise TypeError("obs must be float32 or float64")
+
+
+def smooth_var(obs, params, *, n: int, r: int, want_Vs: bool = False, status=None, stream=None):
+    """Posterior variances of ``smooth``'s output (eks_smooth_var): the
+    covariance recursions alone, time-parallel on the device.
+
+    Returns dict(var=(B,T,n) view of a time-major buffer with
+    var[b,t,j] = c_j Vs_t c_j^T, Vs=(B,T,r,r) or None, status=(B,) int32).
+    A trajectory with an exact observation (zero ensemble variance) is flagged
+    EKS_STATUS_SCAN and NaN; ``smooth(..., want_var=True, check=True)``
+    recomputes those."""
+    torch = _lib.require_gpu()
+    B, T, E, dt = _obs_code(obs, n)
+    if params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
+            or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    dev = obs.device
+    var = torch.empty((T, B, n), dtype=torch.float64, device=dev).permute(1, 0, 2)
+    Vs = torch.empty((B, T, r, r), dtype=torch.float64, device=dev) if want_Vs else None
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = workspace(lib.eks_smooth_var_workspace_bytes(B, T, n, r), dev, slot="smooth_var")
+    yev = isinstance(obs, Yev)
+    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
+    vb, vt, vj = var.stride()
+    _lib.check(lib.eks_smooth_var(
+        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
+        params.data_ptr(), var.data_ptr(), vb, vt, vj,
+        Vs.data_ptr() if Vs is not None else None, ws.data_ptr(), ws.numel(),
+        status.data_ptr(), _lib.stream_ptr(stream)), "eks_smooth_var")
+    return dict(var=var, Vs=Vs, status=status)
+
+
+def _var_unfused(obs, params, rows, *, n: int, r: int, mode: str):
+    """(var (k,T,n), Vs (k,T,r,r), status (k,)) of the trajectories ``rows``
+    through the unfused kernels eks_ensemble -> eks_forward -> eks_backward and
+    a projection: the path for exact observations, which have no W_t."""
+    import torch
+    lib = _lib.load()
+    B, T, E, dt = _obs_code(obs, n)
+    dev = obs.device
+    k = int(rows.numel())
+    f64 = dict(dtype=torch.float64, device=dev)
+    if isinstance(obs, Yev):
+        ysize = 4 if obs.code == _lib.EKS_YEV32 else 8
+        off = (T * n * B * ysize + 255) // 256 * 256
+        planes = obs.buf[off:off + T * n * B * 8].view(torch.float64).reshape(T, n, B)
+        ev = planes[:, :, rows].permute(2, 0, 1).contiguous()
+        y = torch.zeros_like(ev)  # the covariances do not depend on y
+    else:
+        sub = obs[rows]
+        y = torch.empty((k, T, n), **f64)
+        ev = torch.empty((k, T, n), **f64)
+        sb, st, se, sj = sub.stride()
+        _lib.check(lib.eks_ensemble(sub.data_ptr(), dt, k, T, E, n, sb, st, se, sj,
+                                    _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN,
+                                    y.data_ptr(), ev.data_ptr(), _lib.stream_ptr()), "eks_ensemble")
+    p = params[rows]
+    rr = r * r
+    m0 = p[:, :r].contiguous()
+    S0, A, Q = (p[:, r + i * rr:r + (i + 1) * rr].contiguous() for i in range(3))
+    C = p[:, r + 3 * rr:r + 3 * rr + n * r].contiguous()
+    mf = torch.empty((k, T, r), **f64)
+    Vf = torch.empty((k, T, r, r), **f64)
+    S = torch.empty((k, T, r, r), **f64)
+    Vs = torch.empty((k, T, r, r), **f64)
+    st1 = torch.empty((k,), dtype=torch.int32, device=dev)
+    st2 = torch.empty((k,), dtype=torch.int32, device=dev)
+    _lib.check(lib.eks_forward(k, T, n, r, y.data_ptr(), ev.data_ptr(), m0.data_ptr(),
+                               S0.data_ptr(), A.data_ptr(), Q.data_ptr(), C.data_ptr(), None, 0,
+                               mf.data_ptr(), Vf.data_ptr(), S.data_ptr(), None, st1.data_ptr(),
+                               _lib.stream_ptr()), "eks_forward")
+    _lib.check(lib.eks_backward(k, T, r, mf.data_ptr(), Vf.data_ptr(), S.data_ptr(), A.data_ptr(),
+                                0, None, Vs.data_ptr(), None, st2.data_ptr(), _lib.stream_ptr()),
+               "eks_backward")
+    Cm = C.reshape(k, n, r)
+    var = torch.einsum("bji,btik,bjk->btj", Cm, Vs, Cm)
+    return var, Vs, st1 | st2
+
+
 def smooth(obs, params, *, n: int, r: int, mode: str = "median", out=None, want_ms=False,
            want_nll=False, status=None, algo: int = 0, flags: int = 0, stream=None,
-           check: bool = False, want_out: bool = True):
+           check: bool = False, want_out: bool = True, want_var: bool = False,
+           want_Vs: bool = False):
     """Fused ensemble -> forward -> backward -> projection for B trajectories.
 
+    ``want_var`` / ``want_Vs``: the posterior variances of the output,
+    ``var`` (B,T,n) with var[b,t,j] = c_j Vs_t c_j^T, and the smoothed
+    covariances ``Vs`` (B,T,r,r), from the variance pass (``smooth_var``) run
+    after the smoother on the same stream; its status is OR-ed into
+    ``status``.  With ``check=True`` trajectories it flags EKS_STATUS_SCAN
+    (exact observations) are recomputed through the unfused kernels.
+
     Returns dict(out=(B,T,n) view, ms=(B,T,r) or None, nll=(B,) or None,
-    status=(B,) int32 bit mask).  ``out`` (if given) must be a (B, T, n)
+    status=(B,) int32 bit mask, var, Vs (None unless asked for)).  ``out`` (if given) must be a (B, T, n)
     float64 CUDA tensor/view; by default a time-major buffer is allocated so
     that the kernel's stores are coalesced.  ``flags`` are EKS_MODEL_* promises
     (see ``model_flags``); ``algo`` 0 = automatic, 1 = sequential, 2 =
@@ -166,7 +270,12 @@ def smooth(obs, params, *, n: int, r: int, mode: str = "median", out=None, want_
         ms.data_ptr() if ms is not None else None,
         nll.data_ptr() if nll is not None else None, ws.data_ptr(), ws.numel(), flags, algo,
         status.data_ptr(), _lib.stream_ptr(stream)), "eks_smooth")
-    res = dict(out=out, ms=ms, nll=nll, status=status)
+    res = dict(out=out, ms=ms, nll=nll, status=status, var=None, Vs=None)
+    pv = None
+    if want_var or want_Vs:  # the variance pass: own workspace slot, own status until checked
+        pv = smooth_var(obs, params, n=n, r=r, want_Vs=want_Vs, stream=stream)
+        res["var"] = pv["var"] if want_var else None
+        res["Vs"] = pv["Vs"]
     if check:
         st_all = status_bits(status)
         if st_all & _lib.EKS_STATUS_BAD_MODEL:
@@ -174,9 +283,22 @@ def smooth(obs, params, *, n: int, r: int, mode: str = "median", out=None, want_
         if st_all & _lib.EKS_STATUS_SCAN and algo != 1:
             return smooth(obs, params, n=n, r=r, mode=mode, out=out, want_ms=want_ms,
                           want_nll=want_nll, status=status, algo=1, flags=flags,
-                          stream=stream, check=True, want_out=want_out)
+                          stream=stream, check=True, want_out=want_out, want_var=want_var,
+                          want_Vs=want_Vs)
         if st_all & _lib.EKS_STATUS_SINGULAR:
             raise np.linalg.LinAlgError("Singular matrix")
+        if pv is not None and status_bits(pv["status"]) & _lib.EKS_STATUS_SCAN:
+            # exact observations: only the flagged rows, through the unfused kernels
+            rows = torch.nonzero(pv["status"] & _lib.EKS_STATUS_SCAN).flatten()
+            var_r, Vs_r, st_r = _var_unfused(obs, params, rows, n=n, r=r, mode=mode)
+            pv["var"][rows] = var_r
+            if pv["Vs"] is not None:
+                pv["Vs"][rows] = Vs_r
+            pv["status"][rows] = st_r
+        if pv is not None and status_bits(pv["status"]) & _lib.EKS_STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+    if pv is not None:
+        status |= pv["status"]
     return res
 
 

@@ -45,6 +45,7 @@ long long g_a3_mode = 0;
 long long g_a3_lb = 0;
 long long g_rt_form = 0;
 extern long long g_fit_select;  // eks_fit.hip
+extern long long g_pvar_chunk;  // eks_postvar.hip
 }
 
 extern "C" {
@@ -254,6 +255,11 @@ int64_t eks_debug_set(int key, int64_t value) {
     case EKS_DBG_FIT_SELECT: {
       const long long prev = g_fit_select;
       g_fit_select = value == 1 || value == 2 ? value : 0;
+      return prev;
+    }
+    case EKS_DBG_PVAR_CHUNK: {
+      const long long prev = g_pvar_chunk;
+      g_pvar_chunk = value > 0 ? value : 0;
       return prev;
     }
     default: return set_err(EKS_ERR_ARG, "eks_debug_set: unknown key %d", key), -1;

@@ -16,6 +16,7 @@
 //   eks::backward(mf, Vf, S, A)                    :120-164 (smooth_backward)
 //   eks::nll(obs, params, n, r, mode, flags)       compute_nll
 //   eks::smooth(obs, params, n, r, mode, flags, algo)  the fused hot path
+//   eks::smooth_var(obs, params, n, r)             posterior variances of smooth's output
 //   eks::fit(obs, kind, n, r, s, q, mode)          eks/multiview_pca_smoother.py:684-731
 //   eks::newton_filter(y, ev, mu0, S0, A, Bm, E, max_iter)  eks/newton_eks.py:115-148
 //   eks::interp1d(x, y, xq)                        eks/multiview_pca_smoother.py:86-96
@@ -232,6 +233,40 @@ std::tuple<Tensor, Tensor> smooth_meta(const Tensor& obs, const Tensor&, int64_t
   return {at::empty({obs.size(0), obs.size(1), n}, obs.options().dtype(at::kDouble)),
           at::empty({obs.size(0)}, obs.options().dtype(at::kInt))};
 }
+// posterior variances of smooth's output: var (B, T, n), Vs (B, T, r, r)
+std::tuple<Tensor, Tensor, Tensor> smooth_var_gpu(const Tensor& obs, const Tensor& params,
+                                                  int64_t n, int64_t r) {
+  need_gpu(obs, "obs");
+  need_gpu(params, "params");
+  TORCH_CHECK(params.device() == obs.device(), "params is on ", params.device().str(),
+              ", obs on ", obs.device().str());
+  TORCH_CHECK(obs.dim() == 4 && obs.size(3) == n, "obs must be viewed as (B, T, E, n) with n=", n);
+  const c10::DeviceGuard g(obs.device());
+  const int64_t B = obs.size(0), T = obs.size(1), E = obs.size(2);
+  Tensor prm = params.contiguous();
+  TORCH_CHECK(prm.scalar_type() == at::kDouble && prm.dim() == 2 && prm.size(0) == B &&
+                  prm.size(1) == eks_param_len((int)n, (int)r),
+              "params must be a (", B, ", ", eks_param_len((int)n, (int)r), ") float64 tensor");
+  Tensor var_tm = at::empty({T, B, n}, f64(obs));  // time-major: coalesced stores
+  Tensor Vs = at::empty({B, T, r, r}, f64(obs));
+  Tensor status = at::empty({B}, i32(obs));
+  const size_t wsb = eks_smooth_var_workspace_bytes(B, T, (int)n, (int)r);
+  Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 1)}, obs.options().dtype(at::kByte));
+  check(eks_smooth_var(obs.data_ptr(), obs_dtype(obs), B, T, (int)E, (int)n, (int)r,
+                       obs.stride(0), obs.stride(1), obs.stride(2), obs.stride(3),
+                       prm.data_ptr<double>(), var_tm.data_ptr<double>(), n, B * n, 1,
+                       Vs.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel(),
+                       status.data_ptr<int32_t>(), cur_stream(obs)),
+        "eks_smooth_var");
+  return {var_tm.permute({1, 0, 2}).contiguous(), Vs, status};
+}
+std::tuple<Tensor, Tensor, Tensor> smooth_var_meta(const Tensor& obs, const Tensor&, int64_t n,
+                                                   int64_t r) {
+  auto o = obs.options().dtype(at::kDouble);
+  return {at::empty({obs.size(0), obs.size(1), n}, o),
+          at::empty({obs.size(0), obs.size(1), r, r}, o),
+          at::empty({obs.size(0)}, obs.options().dtype(at::kInt))};
+}
 // compute_nll: the filter-only pass; raises where the reference's solve would
 // (singular system) or when a model promise does not hold
 Tensor nll_gpu(const Tensor& obs, const Tensor& params, int64_t n, int64_t r,
@@ -347,6 +382,7 @@ TORCH_LIBRARY(eks, m) {
   m.def("backward(Tensor mf, Tensor Vf, Tensor S, Tensor A) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("smooth(Tensor obs, Tensor params, int n, int r, str mode, int flags, int algo) -> "
         "(Tensor, Tensor)");
+  m.def("smooth_var(Tensor obs, Tensor params, int n, int r) -> (Tensor, Tensor, Tensor)");
   m.def("nll(Tensor obs, Tensor params, int n, int r, str mode, int flags) -> Tensor");
   m.def("fit(Tensor obs, str kind, int n, int r, float smooth_param, float quantile_keep, "
         "str mode) -> (Tensor, Tensor)");
@@ -360,6 +396,7 @@ TORCH_LIBRARY_IMPL(eks, CUDA, m) {
   m.impl("forward", &forward_gpu);
   m.impl("backward", &backward_gpu);
   m.impl("smooth", &smooth_gpu);
+  m.impl("smooth_var", &smooth_var_gpu);
   m.impl("nll", &nll_gpu);
   m.impl("fit", &fit_gpu);
   m.impl("newton_filter", &newton_gpu);
@@ -371,6 +408,7 @@ TORCH_LIBRARY_IMPL(eks, Meta, m) {
   m.impl("forward", &forward_meta);
   m.impl("backward", &backward_meta);
   m.impl("smooth", &smooth_meta);
+  m.impl("smooth_var", &smooth_var_meta);
   m.impl("nll", &nll_meta);
   m.impl("fit", &fit_meta);
   m.impl("newton_filter", &newton_meta);

@@ -19,6 +19,8 @@ CPU tensor is a dispatch error).  Layout conventions are those of
     backward   :120-164 (smooth_backward)          nll       compute_nll
     smooth     the fused hot path                  fit       eks/multiview_pca_smoother.py:684-731
     newton_filter  eks/newton_eks.py:115-148       interp1d  eks/multiview_pca_smoother.py:86-96
+    smooth_var (obs, params, n, r) -> (var (B,T,n), Vs (B,T,r,r), status): the posterior
+               variances diag(C Vs C^T) of smooth's output and the smoothed covariances
 """
 from __future__ import annotations
 
@@ -30,7 +32,8 @@ from . import _lib
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libeks_torch.so")
 
-OPS = ("ensemble", "forward", "backward", "smooth", "nll", "fit", "newton_filter", "interp1d")
+OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "nll", "fit", "newton_filter",
+       "interp1d")
 
 
 def _load():

@@ -24,8 +24,10 @@ from .utils import TRACKER, make_dlc_pandas_index
 
 
 def _run_fused(stack: np.ndarray, model: dict, mode: str = "median", want_ms=False,
-               want_nll=False, yev=None):
-    """stack (E, T, n) float64 host array + model -> out (T, n), ms, nll.
+               want_nll=False, yev=None, want_var=False, want_Vs=False):
+    """stack (E, T, n) float64 host array + model -> out (T, n), ms, nll
+    (and, with ``want_var`` or ``want_Vs``, the posterior variances var (T, n)
+    and covariances Vs (T, r, r) as a fourth and fifth value).
     With ``yev`` (core.ensemble_handoff's planes of the same stack) the
     smoother reads the planes instead of uploading and reducing the members
     again (every algorithm, the runtime-n kernels included)."""
@@ -40,21 +42,27 @@ def _run_fused(stack: np.ndarray, model: dict, mode: str = "median", want_ms=Fal
     params = batch.pack_params(model["m0"], model["S0"], model["A"], model["Q"], model["C"],
                                model["offset"])
     res = batch.smooth(obs, params, n=n, r=r, mode=mode, want_ms=want_ms, want_nll=want_nll,
-                       flags=batch.model_flags(model["A"], model["C"], model["Q"]), check=True)
+                       flags=batch.model_flags(model["A"], model["C"], model["Q"]), check=True,
+                       want_var=want_var, want_Vs=want_Vs)
     out = res["out"][0].cpu().numpy()
     ms = res["ms"][0].cpu().numpy() if want_ms else None
     nll = float(res["nll"][0].item()) if want_nll else None
+    if want_var or want_Vs:
+        return (out, ms, nll, res["var"][0].cpu().numpy() if want_var else None,
+                res["Vs"][0].cpu().numpy() if want_Vs else None)
     return out, ms, nll
 
 
 def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, smooth_param,
-                                       quantile_keep_pca, camera_names):
+                                       quantile_keep_pca, camera_names, posterior_var=False):
     """Multi-view PCA smoother for one keypoint (eks/multiview_pca_smoother.py:611-767).
 
     markers_list_cameras[camera][model] is a DataFrame whose first two
     columns are that camera's x and y predictions.  Returns
     {f'{camera}_df': DataFrame} with (scorer, keypoint, x/y/likelihood)
-    columns; likelihood is NaN as in the reference."""
+    columns; likelihood is NaN as in the reference.  With ``posterior_var``
+    the dict gains 'posterior_var_df': {f'{camera}_df': DataFrame} in the same
+    layout, x / y holding the posterior variances of the smoothed x / y."""
     V = len(camera_names)
     if V < 2:
         raise ValueError("ensemble_kalman_smoother_multi_cam needs at least two cameras "
@@ -66,37 +74,51 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
     stack = np.concatenate(cols, axis=2)  # (E, T, 2V), camera-major columns
     yev, preds, ev = core.ensemble_handoff(stack)
     model = fit.multicam_model(preds, ev, smooth_param, quantile_keep_pca)
-    out, _, _ = _run_fused(stack, model, yev=yev)
+    out, _, _, *pv = _run_fused(stack, model, yev=yev, want_var=bool(posterior_var))
     pdindex = make_dlc_pandas_index([keypoint_ensemble])
     dfs = {}
     nan = np.full(out.shape[0], np.nan)
     for c, cam in enumerate(camera_names):
         arr = np.stack([out[:, 2 * c], out[:, 2 * c + 1], nan], axis=1)
         dfs[cam + "_df"] = pd.DataFrame(arr, columns=pdindex)
+    if posterior_var:
+        dfs["posterior_var_df"] = _camera_dfs(pv[0], keypoint_ensemble, camera_names)
     return dfs
 
 
 def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
-                                   state_transition_matrix):
+                                   state_transition_matrix, posterior_var=False):
     """IBL pupil smoother (eks/pupil_smoother.py:82-223).
 
     Returns {'markers_df': smoothed keypoints in the order top, right, bottom,
-    left (NaN likelihood), 'latents_df': diameter, com_x, com_y}."""
+    left (NaN likelihood), 'latents_df': diameter, com_x, com_y}.  With
+    ``posterior_var`` also 'posterior_var_df' (the markers layout, x / y holding
+    the posterior variances) and 'latents_posterior_var_df' (diag(Vs))."""
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
     yev, preds, _ = core.ensemble_handoff(stack)
     model = fit.pupil_model(preds, state_transition_matrix)
-    out, ms, _ = _run_fused(stack, model, want_ms=True, yev=yev)
-    by_key = {k: out[:, j] for j, k in enumerate(fit.PUPIL_KEYS)}
+    pv = bool(posterior_var)
+    out, ms, _, *var_Vs = _run_fused(stack, model, want_ms=True, yev=yev, want_var=pv, want_Vs=pv)
     nan = np.full(out.shape[0], np.nan)
-    cols = []
-    for kp in ('top', 'right', 'bottom', 'left'):  # output order of :199-203
-        cols += [by_key[f'pupil_{kp}_r_x'], by_key[f'pupil_{kp}_r_y'], nan]
-    markers_df = pd.DataFrame(np.stack(cols, 1), columns=make_dlc_pandas_index(keypoint_names))
+
+    def markers(arr):
+        by_key = {k: arr[:, j] for j, k in enumerate(fit.PUPIL_KEYS)}
+        cols = []
+        for kp in ('top', 'right', 'bottom', 'left'):  # output order of :199-203
+            cols += [by_key[f'pupil_{kp}_r_x'], by_key[f'pupil_{kp}_r_y'], nan]
+        return pd.DataFrame(np.stack(cols, 1), columns=make_dlc_pandas_index(keypoint_names))
+
     lat = np.stack([ms[:, 0], ms[:, 1] + model["mx"], ms[:, 2] + model["my"]], 1)
     idx = pd.MultiIndex.from_arrays([[tracker_name] * 3, ['diameter', 'com_x', 'com_y']],
                                     names=('scorer', 'latent'))
-    return {'markers_df': markers_df, 'latents_df': pd.DataFrame(lat, columns=idx)}
+    res = {'markers_df': markers(out), 'latents_df': pd.DataFrame(lat, columns=idx)}
+    if pv:
+        var, Vs = var_Vs
+        res['posterior_var_df'] = markers(var)
+        res['latents_posterior_var_df'] = pd.DataFrame(
+            np.diagonal(Vs, axis1=1, axis2=2).copy(), columns=idx)
+    return res
 
 
 def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s_grid,
@@ -133,24 +155,31 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
 
 
 def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth_param,
-                                         quantile_keep_pca=25, ensembling_mode="median"):
+                                         quantile_keep_pca=25, ensembling_mode="median",
+                                         posterior_var=False):
     """Single-view EKS for one keypoint (the reference
     snapshot has no single-view smoother).
 
     markers_list: E DataFrames with '{keypoint}_x' / '{keypoint}_y' columns.
     Model: C = A = I2, m0 = 0, S0 = diag(var), Q = s cov(diff) over the
     low-variance frames, offset = their mean.  Returns {'markers_df',
-    'nll'} with the reference's output format."""
+    'nll'} with the reference's output format; with ``posterior_var`` also
+    'posterior_var_df' (the same layout, x / y holding the posterior variances)."""
     keys = [f"{keypoint_ensemble}_x", f"{keypoint_ensemble}_y"]
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in keys], 1)
                       for df in markers_list])  # (E, T, 2)
     yev, preds, ev = core.ensemble_handoff(stack, ensembling_mode)
     model = fit.singleview_model(preds, ev, smooth_param, quantile_keep_pca)
-    out, _, nll = _run_fused(stack, model, mode=ensembling_mode, want_nll=True, yev=yev)
+    out, _, nll, *pv = _run_fused(stack, model, mode=ensembling_mode, want_nll=True, yev=yev,
+                                  want_var=bool(posterior_var))
     nan = np.full(out.shape[0], np.nan)
-    df = pd.DataFrame(np.stack([out[:, 0], out[:, 1], nan], 1),
-                      columns=make_dlc_pandas_index([keypoint_ensemble]))
-    return {'markers_df': df, 'nll': nll}
+    idx = make_dlc_pandas_index([keypoint_ensemble])
+    df = pd.DataFrame(np.stack([out[:, 0], out[:, 1], nan], 1), columns=idx)
+    res = {'markers_df': df, 'nll': nll}
+    if posterior_var:
+        res['posterior_var_df'] = pd.DataFrame(np.stack([pv[0][:, 0], pv[0][:, 1], nan], 1),
+                                               columns=idx)
+    return res
 
 
 

@@ -242,6 +242,38 @@ int eks_smooth_plan_info(int64_t B, int64_t T, int n, int r, int E, int algo,
                          int smoothing /* out != NULL */, int64_t *info, int n_info);
 
 /*
+ * eks_smooth_var -- the posterior variances of eks_smooth's output: the
+ * covariance recursions of eks/ensemble_kalman.py:59-164 alone (Vf, S, the
+ * RTS gain and Vs do not depend on the observations), time-parallel over
+ * chunks, with R_t = diag(ev[t]), ev the ensemble variances eks_smooth uses.
+ *
+ *   obs      member observations, strides as eks_ensemble (EKS_F32 / EKS_F64),
+ *            or the y / ev hand-off planes of eks_fit (EKS_YEV32 / EKS_YEV64;
+ *            strides ignored, only the ev planes are read)
+ *   params   (B, P) f64 packed models (see eks_param_len); m0 and offset unused
+ *   pvar     pvar(b,t,j) = c_j Vs_t c_j^T = pvar[b*vb + t*vt + j*vj] (f64), the
+ *            variance of out(b,t,j); REQUIRED
+ *   Vs       (B, T, r, r) contiguous smoothed covariances, or NULL
+ *   status   (B) int32, REQUIRED; zeroed by the call.  EKS_STATUS_SINGULAR
+ *            where the smoother's S_t is singular; EKS_STATUS_SCAN for a
+ *            trajectory with an exact observation (ev[t][j] == 0: a single
+ *            member or identical members), whose pvar / Vs are NaN -- run
+ *            those through eks_ensemble / eks_forward / eks_backward.
+ *            Other trajectories are unaffected; a NaN ev makes the
+ *            trajectory NaN and is not an error.
+ * r = 2 or 3, n <= 64 (the runtime-n smoother's limit), E <= eks_max_members(),
+ * else EKS_ERR_UNSUPPORTED.  There are no model_flags: the general model runs.
+ * eks_smooth_var_chunk_len: the chunk length as launched (a single chunk
+ * covering T is the sequential form); EKS_DBG_PVAR_CHUNK forces it.
+ */
+size_t eks_smooth_var_workspace_bytes(int64_t B, int64_t T, int n, int r);
+int64_t eks_smooth_var_chunk_len(int64_t B, int64_t T, int r);
+int eks_smooth_var(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
+                   int64_t sb, int64_t st, int64_t se, int64_t sj, const double *params,
+                   double *pvar, int64_t vb, int64_t vt, int64_t vj, double *Vs, void *workspace,
+                   size_t workspace_bytes, int32_t *status, void *stream);
+
+/*
  * Time-sharded smoothing (SURVEY.md §8(e) "shard the time axis"): the frames
  * of every trajectory are split into nseg contiguous segments, segment k on
  * rank k, and the chunked scan of eks_smooth runs per segment in three
@@ -375,9 +407,13 @@ int eks_interp1d(const double *x, int64_t nx, const double *y, int64_t ncol, int
  *                          fill the GPU), 1 = one lane per trajectory, 2 =
  *                          time-parallel.  Results agree to rounding; set it
  *                          before eks_smooth_workspace_bytes.
+ *   EKS_DBG_PVAR_CHUNK     eks_smooth_var's chunk length: 0 = automatic, else
+ *                          that many steps rounded up to a multiple of 8
+ *                          (>= T: one chunk).  Set it before
+ *                          eks_smooth_var_workspace_bytes.
  */
 enum { EKS_DBG_WAIT_US = 1, EKS_DBG_A3_SLICE_BYTES = 2, EKS_DBG_FIT_SELECT = 3,
-       EKS_DBG_A3_MODE = 4, EKS_DBG_A3_LB = 5, EKS_DBG_RT_FORM = 6 };
+       EKS_DBG_A3_MODE = 4, EKS_DBG_A3_LB = 5, EKS_DBG_RT_FORM = 6, EKS_DBG_PVAR_CHUNK = 7 };
 int64_t eks_debug_set(int key, int64_t value);
 
 /*
