@@ -364,6 +364,156 @@ def nll(obs, params, *, n: int, r: int, mode: str = "median", flags: int = 0, al
                   want_out=False, status=status)["nll"]
 
 
+def _yev_rows(obs: Yev, rows):
+    """The hand-off planes of the trajectories ``rows`` as a Yev of their own."""
+    import torch
+    B, T, E, n = obs.shape
+    ysize, ydt = (4, torch.float32) if obs.code == _lib.EKS_YEV32 else (8, torch.float64)
+    off = (T * n * B * ysize + 255) // 256 * 256
+    y = obs.buf[:T * n * B * ysize].view(ydt).reshape(T * n, B)[:, rows].contiguous()
+    ev = obs.buf[off:off + T * n * B * 8].view(torch.float64).reshape(T * n, B)[:, rows].contiguous()
+    k = int(rows.numel())
+    off2 = (T * n * k * ysize + 255) // 256 * 256
+    buf = torch.zeros(off2 + T * n * k * 8, dtype=torch.uint8, device=obs.device)
+    buf[:T * n * k * ysize] = y.view(torch.uint8).flatten()
+    buf[off2:] = ev.view(torch.uint8).flatten()
+    return Yev(buf, k, T, E, n, obs.code, obs.mode)
+
+
+def nll_sweep(obs, params, *, K: int, n: int, r: int, mode: str = "median", check: bool = True,
+              status=None, stream=None):
+    """The innovation NLL of K candidate models for each of B trajectories in
+    one call (eks_nll_sweep): the members (or the hand-off planes) are read
+    and reduced once for all candidates, and a candidate costs r scalar
+    updates per step whatever n is.
+
+    ``params`` is (K * B, P): row k * B + b is candidate k of trajectory b.
+    The candidates of a trajectory may differ in m0, S0, A and Q; C and
+    offset must be equal.  Returns the (K, B) float64 NLLs; ``status`` (K, B)
+    int32 receives the status bits.  With ``check=True`` the call
+    synchronises: trajectories flagged EKS_STATUS_SCAN (an exact observation,
+    a C without full column rank: NaN here) are recomputed with ``nll``, one
+    call per candidate on the flagged trajectories; EKS_STATUS_BAD_MODEL (C or
+    offset differ between candidates) raises ValueError, EKS_STATUS_SINGULAR
+    LinAlgError."""
+    torch = _lib.require_gpu()
+    B, T, E, dt = _obs_code(obs, n)
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    yev = isinstance(obs, Yev)
+    if yev and mode != obs.mode:
+        raise ValueError("the hand-off planes were made in another averaging mode")
+    P = param_len(n, r)
+    if K < 0 or params.shape != (K * B, P) or params.dtype != torch.float64 \
+            or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous ({K * B}, {P}) float64 tensor")
+    dev = obs.device
+    out = torch.empty((K, B), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty((K, B), dtype=torch.int32, device=dev)
+    elif status.shape != (K, B) or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError(f"status must be a contiguous ({K}, {B}) int32 tensor")
+    lib = _lib.load()
+    ws = workspace(lib.eks_nll_sweep_workspace_bytes(B, K, T, n, r), dev, slot="nll_sweep")
+    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
+    _lib.check(lib.eks_nll_sweep(
+        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
+        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(), K,
+        out.data_ptr(), ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)),
+        "eks_nll_sweep")
+    if check and K * B > 0:
+        bits = status_bits(status)
+        if bits & _lib.EKS_STATUS_BAD_MODEL:
+            raise ValueError("the candidates of a trajectory must share C and offset")
+        if bits & _lib.EKS_STATUS_SCAN:
+            rows = torch.nonzero(((status & _lib.EKS_STATUS_SCAN) != 0).any(dim=0)).flatten()
+            sub = _yev_rows(obs, rows) if yev else obs[rows]
+            cand = params.view(K, B, P)
+            for k in range(K):
+                out[k, rows] = nll(sub, cand[k, rows].contiguous(), n=n, r=r, mode=mode,
+                                   check=True)
+            status[:, rows] &= ~_lib.EKS_STATUS_SCAN
+        if status_bits(status) & _lib.EKS_STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+    return out
+
+
+DEFAULT_SWEEP_GRID = tuple(10.0 ** e for e in range(-4, 5))
+
+
+def sweep_bracket(grid, best):
+    """The next round's grid of a likelihood sweep (a pure function of torch
+    tensors on any device): ``grid`` (B, K) ascending per row, ``best`` (B,)
+    the index of each row's minimum -> (B, K): K log-spaced points from the
+    best point's lower neighbour to its upper neighbour, both included,
+    clipped at the row's ends (a best point at an end keeps that end)."""
+    import torch
+    K = grid.shape[1]
+    lo = torch.gather(grid, 1, (best - 1).clamp(min=0).unsqueeze(1))
+    hi = torch.gather(grid, 1, (best + 1).clamp(max=K - 1).unsqueeze(1))
+    if K == 1:
+        return lo.clone()
+    frac = torch.arange(K, dtype=grid.dtype, device=grid.device) / (K - 1)
+    new = lo * (hi / lo) ** frac
+    new[:, 0] = lo[:, 0]
+    new[:, -1] = hi[:, 0]
+    return new
+
+
+def scale_q(params, s, *, r: int):
+    """params (B, P) rows -> (K, B, P) rows with Q scaled by s (K, B), on the
+    device of ``params``."""
+    K, B = s.shape
+    rows = params.unsqueeze(0).repeat(K, 1, 1)
+    q0 = r + 2 * r * r
+    rows[:, :, q0:q0 + r * r] *= s.unsqueeze(2)
+    return rows
+
+
+def select_smooth_param(obs, params, *, n: int, r: int, mode: str = "median", grid=None,
+                        refine: int = 2):
+    """The smoothing parameter of every trajectory chosen by likelihood on the
+    device, as the reference's later versions do for ``smooth_param=None``.
+
+    ``params`` holds B rows fitted with ``smooth_param = 1`` (Q = Q0).  Every
+    round scores K candidates Q = s Q0 per trajectory in one ``nll_sweep``
+    call (the K * B rows are built on the device by scaling the Q slice) and
+    takes the per-trajectory argmin, ties to the smallest s; the next round
+    lays K log-spaced points between the best point's two neighbours
+    (``sweep_bracket``).  The default grid is 10 ** arange(-4, 5); after
+    ``refine`` = 2 rounds its spacing is 10 ** (1 / 16).  A later round
+    replaces the choice only where it lowers the NLL.
+
+    Returns dict(smooth_param (B,), nll (B,), at_edge (B,) bool: the choice is
+    the grid's first or last point, params (B, P): the rows with Q scaled)."""
+    torch = _lib.require_gpu()
+    B = params.shape[0]
+    dev = params.device
+    g0 = torch.as_tensor(DEFAULT_SWEEP_GRID if grid is None else np.asarray(grid, dtype=np.float64),
+                         dtype=torch.float64, device=dev)
+    if g0.dim() != 1 or g0.numel() < 1 or bool((g0[1:] <= g0[:-1]).any()) or bool((g0 <= 0).any()):
+        raise ValueError("grid must be a positive, strictly ascending 1-D sequence")
+    K = int(g0.numel())
+    g = g0.unsqueeze(0).repeat(B, 1)  # (B, K)
+    best_s = best_nll = None
+    for rnd in range(int(refine) + 1):
+        rows = scale_q(params, g.t().contiguous(), r=r)
+        scores = nll_sweep(obs, rows.view(K * B, -1), K=K, n=n, r=r, mode=mode).t()  # (B, K)
+        idx = torch.argmin(scores, dim=1)  # the first minimum: the smallest s
+        s = torch.gather(g, 1, idx.unsqueeze(1))[:, 0]
+        v = torch.gather(scores, 1, idx.unsqueeze(1))[:, 0]
+        if best_s is None:
+            best_s, best_nll = s, v
+        else:
+            better = v < best_nll
+            best_s = torch.where(better, s, best_s)
+            best_nll = torch.where(better, v, best_nll)
+        g = sweep_bracket(g, idx)
+    at_edge = (best_s == g0[0]) | (best_s == g0[-1])
+    return dict(smooth_param=best_s, nll=best_nll, at_edge=at_edge,
+                params=scale_q(params, best_s.unsqueeze(0), r=r)[0])
+
+
 def status_bits(status) -> int:
     """OR of all per-trajectory status words (synchronises)."""
     v = 0

@@ -21,6 +21,8 @@ CPU tensor is a dispatch error).  Layout conventions are those of
     newton_filter  eks/newton_eks.py:115-148       interp1d  eks/multiview_pca_smoother.py:86-96
     smooth_var (obs, params, n, r) -> (var (B,T,n), Vs (B,T,r,r), status): the posterior
                variances diag(C Vs C^T) of smooth's output and the smoothed covariances
+    nll_sweep  (obs, params (K*B, P), K, n, r, mode) -> (nll (K,B), status (K,B)): the NLL
+               of K candidate models per trajectory, the members reduced once
 """
 from __future__ import annotations
 
@@ -32,8 +34,8 @@ from . import _lib
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libeks_torch.so")
 
-OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "nll", "fit", "newton_filter",
-       "interp1d")
+OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "nll", "nll_sweep", "fit",
+       "newton_filter", "interp1d")
 
 
 def _load():

@@ -13,6 +13,11 @@ def resolve_save_dir(save_dir):
     return save_dir
 
 
+def smooth_arg(text: str):
+    """--s: a number, or 'auto' (None: chosen by likelihood on the device)."""
+    return None if text.strip().lower() == "auto" else float(text)
+
+
 def example_plot(markers_list, member_col, eks_df, eks_col, title, save_file):
     """Members (grey) and EKS (black) for frames 0-500 of one keypoint, three
     panels x / y / likelihood, saved as PDF.  Skipped without matplotlib."""

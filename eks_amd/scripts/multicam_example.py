@@ -3,7 +3,7 @@ files as the reference's scripts/multicam_example.py:13-201.
 
     python -m eks_amd.scripts.multicam_example --csv-dir DIR \
         --bodypart-list paw1LH paw2LF --camera-names top bot \
-        [--save-dir OUT] [--s 0.01] [--quantile_keep_pca 25] --eks_version {opti,standard}
+        [--save-dir OUT] [--s 0.01 | --s auto] [--quantile_keep_pca 25] --eks_version {opti,standard}
 
 Writes <save-dir>/eks.csv (or eks_opti.csv for --eks_version opti) in the
 input CSVs' 3-row header format with scorer 'ensemble-kalman_tracker' and
@@ -21,6 +21,8 @@ import sys
 
 import numpy as np
 
+from eks_amd.scripts._common import smooth_arg
+
 
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -31,8 +33,10 @@ def build_parser():
     p.add_argument('--camera-names', required=True, nargs='+', help='the camera names')
     p.add_argument('--save-dir', default=None, type=str,
                    help='save directory for outputs (default is ./outputs)')
-    p.add_argument('--s', default=.01, type=float,
-                   help='smoothing parameter ranges from .01-2 (smaller values = more smoothing)')
+    p.add_argument('--s', default=.01, type=smooth_arg,
+                   help='smoothing parameter ranges from .01-2 (smaller values = more smoothing), '
+                        'or "auto": chosen per body part by minimising the filter NLL '
+                        '(standard version)')
     p.add_argument('--quantile_keep_pca', default=25, type=float,
                    help='percentage of the points are kept for multi-view PCA '
                         '(lowest ensemble variance)')
@@ -77,6 +81,10 @@ def run(args) -> str:
     opti = args.eks_version == "opti"
     out = multi_cam_batch(np.stack(stacks), args.s, args.quantile_keep_pca,
                           version="opti" if opti else "standard")
+    if args.s is None:
+        out, chosen = out
+        for kp, sv in zip(args.bodypart_list, chosen):
+            print(f'smooth_param {kp}: {sv:.6g}')
     for k, kp in enumerate(args.bodypart_list):
         for c, cam in enumerate(cams):
             for j, coord in enumerate(('x', 'y')):

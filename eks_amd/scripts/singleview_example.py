@@ -1,7 +1,7 @@
 """Single-view EKS for one or many videos from the command line.
 
     python -m eks_amd.scripts.singleview_example --csv-dir VIDEO_DIR [VIDEO_DIR ...] \
-        [--bodypart-list kp1 kp2 ...] [--save-dir OUT] [--s 0.01] [--quantile_keep_pca 25] \
+        [--bodypart-list kp1 kp2 ...] [--save-dir OUT] [--s 0.01 | --s auto] [--quantile_keep_pca 25] \
         [--ensembling-mode median]
 
 Each VIDEO_DIR holds the E ensemble members' DLC/LP CSVs of one video (the
@@ -25,6 +25,8 @@ from collections import defaultdict
 
 import numpy as np
 
+from eks_amd.scripts._common import smooth_arg
+
 
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -34,8 +36,9 @@ def build_parser():
                    help='body parts to smooth (default: all)')
     p.add_argument('--save-dir', default=None, type=str,
                    help='save directory for outputs (default is ./outputs)')
-    p.add_argument('--s', default=.01, type=float,
-                   help='smoothing parameter (smaller values = more smoothing)')
+    p.add_argument('--s', default=.01, type=smooth_arg,
+                   help='smoothing parameter (smaller values = more smoothing), or "auto": '
+                        'chosen per body part by minimising the filter NLL')
     p.add_argument('--quantile_keep_pca', default=25, type=float,
                    help='percentage of lowest-variance frames used to fit the model')
     p.add_argument('--ensembling-mode', default='median', choices=['median', 'mean'])
@@ -65,8 +68,15 @@ def run(args):
         stacks = np.concatenate([videos[i]["stack"] for i in members])  # (B, E, T, 2)
         d = torch.from_numpy(np.ascontiguousarray(stacks, dtype=np.float64)).to("cuda")
         obs = d.permute(0, 2, 1, 3)                                      # (B, T, E, 2) view
-        params, _ = batch.fit(obs, kind="singleview", n=2, r=2, smooth_param=args.s,
+        auto = args.s is None
+        params, _ = batch.fit(obs, kind="singleview", n=2, r=2, smooth_param=1.0 if auto else args.s,
                               quantile_keep=args.quantile_keep_pca, mode=args.ensembling_mode)
+        if auto:
+            sel = batch.select_smooth_param(obs, params, n=2, r=2, mode=args.ensembling_mode)
+            params = sel["params"]
+            names = [(videos[i]["dir"], kp) for i in members for kp in videos[i]["bps"]]
+            for (vd, kp), sv in zip(names, sel["smooth_param"].cpu().numpy()):
+                print(f'smooth_param {kp} ({vd}): {sv:.6g}')
         res = batch.smooth(obs, params, n=2, r=2, mode=args.ensembling_mode,
                            flags=_lib.EKS_MODEL_A_IDENTITY | _lib.EKS_MODEL_C_IDENTITY,
                            check=True)

@@ -53,9 +53,25 @@ def _run_fused(stack: np.ndarray, model: dict, mode: str = "median", want_ms=Fal
     return out, ms, nll
 
 
+def _auto_smooth_param(yev, model: dict, mode: str = "median") -> float:
+    """The smoothing parameter chosen by likelihood (batch.select_smooth_param)
+    for one keypoint: ``model`` fitted with smooth_param = 1, ``yev`` the
+    hand-off planes the smoother will read."""
+    n, r = len(model["offset"]), len(model["m0"])
+    params = batch.pack_params(model["m0"], model["S0"], model["A"], model["Q"], model["C"],
+                               model["offset"])
+    sel = batch.select_smooth_param(yev, params, n=n, r=r, mode=mode)
+    return float(sel["smooth_param"][0].item())
+
+
 def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, smooth_param,
                                        quantile_keep_pca, camera_names, posterior_var=False):
     """Multi-view PCA smoother for one keypoint (eks/multiview_pca_smoother.py:611-767).
+
+    ``smooth_param=None``: chosen by minimising the filter's NLL on the device
+    (batch.select_smooth_param); the dict then gains 'smooth_param', and the
+    frames equal those of a call with that value.
+
 
     markers_list_cameras[camera][model] is a DataFrame whose first two
     columns are that camera's x and y predictions.  Returns
@@ -73,10 +89,16 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
                       for e in range(n_models)]) for c in range(V)]  # V x (E, T, 2)
     stack = np.concatenate(cols, axis=2)  # (E, T, 2V), camera-major columns
     yev, preds, ev = core.ensemble_handoff(stack)
+    auto = smooth_param is None
+    if auto:
+        smooth_param = _auto_smooth_param(
+            yev, fit.multicam_model(preds, ev, 1.0, quantile_keep_pca))
     model = fit.multicam_model(preds, ev, smooth_param, quantile_keep_pca)
     out, _, _, *pv = _run_fused(stack, model, yev=yev, want_var=bool(posterior_var))
     pdindex = make_dlc_pandas_index([keypoint_ensemble])
     dfs = {}
+    if auto:
+        dfs["smooth_param"] = smooth_param
     nan = np.full(out.shape[0], np.nan)
     for c, cam in enumerate(camera_names):
         arr = np.stack([out[:, 2 * c], out[:, 2 * c + 1], nan], axis=1)
@@ -164,11 +186,18 @@ def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth
     Model: C = A = I2, m0 = 0, S0 = diag(var), Q = s cov(diff) over the
     low-variance frames, offset = their mean.  Returns {'markers_df',
     'nll'} with the reference's output format; with ``posterior_var`` also
-    'posterior_var_df' (the same layout, x / y holding the posterior variances)."""
+    'posterior_var_df' (the same layout, x / y holding the posterior variances).
+    ``smooth_param=None``: chosen by minimising the filter's NLL on the device
+    (batch.select_smooth_param); the dict then gains 'smooth_param', and the
+    frames equal those of a call with that value."""
     keys = [f"{keypoint_ensemble}_x", f"{keypoint_ensemble}_y"]
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in keys], 1)
                       for df in markers_list])  # (E, T, 2)
     yev, preds, ev = core.ensemble_handoff(stack, ensembling_mode)
+    auto = smooth_param is None
+    if auto:
+        smooth_param = _auto_smooth_param(
+            yev, fit.singleview_model(preds, ev, 1.0, quantile_keep_pca), ensembling_mode)
     model = fit.singleview_model(preds, ev, smooth_param, quantile_keep_pca)
     out, _, nll, *pv = _run_fused(stack, model, mode=ensembling_mode, want_nll=True, yev=yev,
                                   want_var=bool(posterior_var))
@@ -176,6 +205,8 @@ def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth
     idx = make_dlc_pandas_index([keypoint_ensemble])
     df = pd.DataFrame(np.stack([out[:, 0], out[:, 1], nan], 1), columns=idx)
     res = {'markers_df': df, 'nll': nll}
+    if auto:
+        res['smooth_param'] = smooth_param
     if posterior_var:
         res['posterior_var_df'] = pd.DataFrame(np.stack([pv[0][:, 0], pv[0][:, 1], nan], 1),
                                                columns=idx)
@@ -277,17 +308,31 @@ def multi_cam_batch(stacks, smooth_param, quantile_keep_pca, version: str = "sta
     keypoint's model on the device (eks_fit, 1-8 cameras) and runs the fused
     RTS smoother (eks_smooth) on the fit's ensemble hand-off planes, "opti"
     fits on the host and runs the Newton filter (eks_newton_filter,
-    :777-933).  Returns out (K, T, 2V) float64 numpy."""
+    :777-933).  Returns out (K, T, 2V) float64 numpy.
+
+    ``smooth_param=None`` ("standard", up to 8 cameras): every keypoint's
+    smoothing parameter is chosen by likelihood on the device
+    (batch.select_smooth_param) from the fit's hand-off planes; returns
+    (out, smooth_param (K,) float64 numpy)."""
     torch = _lib.require_gpu()
     stacks = np.asarray(stacks, dtype=np.float64)
     K, E, T, n = stacks.shape
     if n < 4:
         raise ValueError("multi-camera smoothing needs at least two cameras")
+    auto = smooth_param is None
+    if auto and (version == "opti" or n % 2 or n > 16):
+        raise ValueError("smooth_param=None needs version 'standard' and at most 8 cameras")
     if version != "opti" and n % 2 == 0 and n <= 16:
         obs = torch.from_numpy(np.ascontiguousarray(stacks)).to("cuda").permute(0, 2, 1, 3)
-        params, _, yev = batch.fit(obs, kind="multicam", n=n, r=3, smooth_param=smooth_param,
+        params, _, yev = batch.fit(obs, kind="multicam", n=n, r=3,
+                                   smooth_param=1.0 if auto else smooth_param,
                                    quantile_keep=quantile_keep_pca, keep_yev=True)
+        if auto:
+            sel = batch.select_smooth_param(yev, params, n=n, r=3)
+            params = sel["params"]
         res = batch.smooth(yev, params, n=n, r=3, flags=_lib.EKS_MODEL_A_IDENTITY, check=True)
+        if auto:
+            return res["out"].cpu().numpy(), sel["smooth_param"].cpu().numpy()
         return res["out"].cpu().numpy()
     d, preds_d, ev_d = ensemble_stacks(stacks)
     preds, ev = preds_d.cpu().numpy(), ev_d.cpu().numpy()

@@ -274,6 +274,44 @@ int eks_smooth_var(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, 
                    size_t workspace_bytes, int32_t *status, void *stream);
 
 /*
+ * eks_nll_sweep -- the innovation NLL (compute_nll; eks_smooth with out = NULL)
+ * of K candidate models for each of B trajectories, in one call: the members
+ * are read and reduced once for all candidates, and a candidate costs r
+ * scalar updates per step whatever n is (the n observations of a step are
+ * reduced to r scalar observations and a model-free constant).
+ *
+ *   obs      member observations, strides as eks_ensemble (EKS_F32 / EKS_F64),
+ *            or the y / ev hand-off planes of eks_fit (EKS_YEV32 / EKS_YEV64;
+ *            strides ignored)
+ *   params   (K * B, P) f64 packed models (see eks_param_len): row k * B + b
+ *            is candidate k of trajectory b.  The candidates of a trajectory
+ *            may differ in m0, S0, A and Q; C and offset must equal
+ *            candidate 0's bit for bit.
+ *   nll      (K, B) f64, REQUIRED
+ *   status   (K, B) int32, REQUIRED; zeroed by the call.  EKS_STATUS_SCAN on
+ *            every candidate of a trajectory this path does not serve -- an
+ *            exact observation (ev[t][j] == 0: a single member or identical
+ *            members) or a C without full column rank (n < r included) -- whose
+ *            NLLs are NaN: run those through eks_smooth with out = NULL.
+ *            EKS_STATUS_BAD_MODEL on a row whose C or offset differ from
+ *            candidate 0's; EKS_STATUS_SINGULAR where the filter's innovation
+ *            variance is not positive.  Other trajectories are unaffected; a
+ *            NaN member makes the NLLs of its trajectory NaN and is not an error.
+ * r = 2 or 3, n <= 64, E <= eks_max_members(), K * B <= 2^28, else
+ * EKS_ERR_UNSUPPORTED (the size queries return 0).  B = 0 or K = 0: EKS_OK,
+ * nothing launched.  Results are bit-reproducible.
+ * eks_nll_sweep_chunk_len: the chunk length as launched (a single chunk
+ * covering T is the sequential form); EKS_DBG_SWEEP_CHUNK forces it.
+ */
+size_t eks_nll_sweep_workspace_bytes(int64_t B, int64_t K, int64_t T, int n, int r);
+int64_t eks_nll_sweep_chunk_len(int64_t B, int64_t K, int64_t T, int r);
+int eks_nll_sweep(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
+                  int64_t sb, int64_t st, int64_t se, int64_t sj, int mode,
+                  const double *params /* (K*B, P): row k*B+b = candidate k of trajectory b */,
+                  int64_t K, double *nll /* (K, B) */, void *workspace, size_t workspace_bytes,
+                  int32_t *status /* (K, B), required, zeroed by the call */, void *stream);
+
+/*
  * Time-sharded smoothing (SURVEY.md §8(e) "shard the time axis"): the frames
  * of every trajectory are split into nseg contiguous segments, segment k on
  * rank k, and the chunked scan of eks_smooth runs per segment in three
@@ -411,9 +449,12 @@ int eks_interp1d(const double *x, int64_t nx, const double *y, int64_t ncol, int
  *                          that many steps rounded up to a multiple of 8
  *                          (>= T: one chunk).  Set it before
  *                          eks_smooth_var_workspace_bytes.
+ *   EKS_DBG_SWEEP_CHUNK    eks_nll_sweep's chunk length, with the same rule.
+ *                          Set it before eks_nll_sweep_workspace_bytes.
  */
 enum { EKS_DBG_WAIT_US = 1, EKS_DBG_A3_SLICE_BYTES = 2, EKS_DBG_FIT_SELECT = 3,
-       EKS_DBG_A3_MODE = 4, EKS_DBG_A3_LB = 5, EKS_DBG_RT_FORM = 6, EKS_DBG_PVAR_CHUNK = 7 };
+       EKS_DBG_A3_MODE = 4, EKS_DBG_A3_LB = 5, EKS_DBG_RT_FORM = 6, EKS_DBG_PVAR_CHUNK = 7,
+       EKS_DBG_SWEEP_CHUNK = 8 };
 int64_t eks_debug_set(int key, int64_t value);
 
 /*
