@@ -438,6 +438,65 @@ def nll_sweep(obs, params, *, K: int, n: int, r: int, mode: str = "median", chec
     return out
 
 
+def smooth_gaps(obs, params, *, n: int, r: int, mode: str = "median", want_var: bool = False,
+                want_Vs: bool = False, want_ms: bool = False, want_nll: bool = False,
+                check: bool = False, status=None, stream=None):
+    """Smoothing through missing observations (eks_smooth_gaps).  Column
+    (t, j) of a trajectory is missing iff its ensemble average or variance is
+    not finite (any NaN or +-inf member; a non-finite y or ev of a ``Yev``):
+    it is left out of the update, and ``out`` / ``var`` are written for every
+    (t, j), missing or not.  A caller who rejects a prediction writes NaN
+    into it; there is no mask argument.
+
+    Returns dict(out=(B,T,n) view of a time-major buffer, var (the same, or
+    None), Vs=(B,T,r,r) or None, ms=(B,T,r) or None, nll=(B,) the innovation
+    NLL over the observed entries or None, nobs=(B,) int32 observed entries,
+    status=(B,) int32).  With ``check=True`` the call synchronises and raises
+    LinAlgError on EKS_STATUS_SINGULAR and ValueError on EKS_STATUS_SCAN (an
+    observed column with zero ensemble variance); there is no fallback path."""
+    torch = _lib.require_gpu()
+    B, T, E, dt = _obs_code(obs, n)
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    yev = isinstance(obs, Yev)
+    if yev and mode != obs.mode:
+        raise ValueError("the hand-off planes were made in another averaging mode")
+    if params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
+            or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    dev = obs.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = torch.empty((T, B, n), **f64).permute(1, 0, 2)
+    var = torch.empty((T, B, n), **f64).permute(1, 0, 2) if want_var else None
+    Vs = torch.empty((B, T, r, r), **f64) if want_Vs else None
+    ms = torch.empty((B, T, r), **f64) if want_ms else None
+    nll_ = torch.empty((B,), **f64) if want_nll else None
+    nobs = torch.empty((B,), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = workspace(lib.eks_smooth_gaps_workspace_bytes(B, T, n, r), dev, slot="smooth_gaps")
+    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
+    ob, ot, oj = out.stride()
+
+    def ptr(x):
+        return x.data_ptr() if x is not None else None
+
+    _lib.check(lib.eks_smooth_gaps(
+        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
+        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(),
+        out.data_ptr(), ob, ot, oj, ptr(var), ptr(ms), ptr(Vs), ptr(nll_), nobs.data_ptr(),
+        ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)), "eks_smooth_gaps")
+    if check and B > 0:
+        bits = status_bits(status)
+        if bits & _lib.EKS_STATUS_SCAN:
+            raise ValueError("an observed column with zero ensemble variance: eks_smooth_gaps "
+                             "does not serve it")
+        if bits & _lib.EKS_STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+    return dict(out=out, var=var, Vs=Vs, ms=ms, nll=nll_, nobs=nobs, status=status)
+
+
 DEFAULT_SWEEP_GRID = tuple(10.0 ** e for e in range(-4, 5))
 
 

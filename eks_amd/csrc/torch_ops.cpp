@@ -17,6 +17,7 @@
 //   eks::nll(obs, params, n, r, mode, flags)       compute_nll
 //   eks::smooth(obs, params, n, r, mode, flags, algo)  the fused hot path
 //   eks::smooth_var(obs, params, n, r)             posterior variances of smooth's output
+//   eks::smooth_gaps(obs, params, n, r, mode)      the smoother through missing observations
 //   eks::nll_sweep(obs, params, K, n, r, mode)     the NLL of K candidate models per trajectory
 //   eks::fit(obs, kind, n, r, s, q, mode)          eks/multiview_pca_smoother.py:684-731
 //   eks::newton_filter(y, ev, mu0, S0, A, Bm, E, max_iter)  eks/newton_eks.py:115-148
@@ -268,6 +269,48 @@ std::tuple<Tensor, Tensor, Tensor> smooth_var_meta(const Tensor& obs, const Tens
           at::empty({obs.size(0), obs.size(1), r, r}, o),
           at::empty({obs.size(0)}, obs.options().dtype(at::kInt))};
 }
+// smoothing through missing observations (a non-finite ensemble average or
+// variance): out, var (B, T, n), nll (B), nobs (B) int32, status (B)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> smooth_gaps_gpu(const Tensor& obs,
+                                                                   const Tensor& params, int64_t n,
+                                                                   int64_t r,
+                                                                   const std::string& mode) {
+  need_gpu(obs, "obs");
+  need_gpu(params, "params");
+  TORCH_CHECK(params.device() == obs.device(), "params is on ", params.device().str(),
+              ", obs on ", obs.device().str());
+  TORCH_CHECK(obs.dim() == 4 && obs.size(3) == n, "obs must be viewed as (B, T, E, n) with n=", n);
+  const c10::DeviceGuard g(obs.device());
+  const int64_t B = obs.size(0), T = obs.size(1), E = obs.size(2);
+  Tensor prm = params.contiguous();
+  TORCH_CHECK(prm.scalar_type() == at::kDouble && prm.dim() == 2 && prm.size(0) == B &&
+                  prm.size(1) == eks_param_len((int)n, (int)r),
+              "params must be a (", B, ", ", eks_param_len((int)n, (int)r), ") float64 tensor");
+  Tensor out_tm = at::empty({T, B, n}, f64(obs));  // time-major: coalesced stores
+  Tensor var_tm = at::empty({T, B, n}, f64(obs));
+  Tensor nll = at::empty({B}, f64(obs));
+  Tensor nobs = at::empty({B}, i32(obs));
+  Tensor status = at::empty({B}, i32(obs));
+  const size_t wsb = eks_smooth_gaps_workspace_bytes(B, T, (int)n, (int)r);
+  Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 1)}, obs.options().dtype(at::kByte));
+  check(eks_smooth_gaps(obs.data_ptr(), obs_dtype(obs), B, T, (int)E, (int)n, (int)r,
+                        obs.stride(0), obs.stride(1), obs.stride(2), obs.stride(3),
+                        mode_code(mode), prm.data_ptr<double>(), out_tm.data_ptr<double>(), n,
+                        B * n, 1, var_tm.data_ptr<double>(), nullptr, nullptr,
+                        nll.data_ptr<double>(), nobs.data_ptr<int32_t>(), ws.data_ptr(),
+                        (size_t)ws.numel(), status.data_ptr<int32_t>(), cur_stream(obs)),
+        "eks_smooth_gaps");
+  return {out_tm.permute({1, 0, 2}).contiguous(), var_tm.permute({1, 0, 2}).contiguous(), nll,
+          nobs, status};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> smooth_gaps_meta(const Tensor& obs,
+                                                                    const Tensor&, int64_t n,
+                                                                    int64_t, const std::string&) {
+  auto o = obs.options().dtype(at::kDouble);
+  auto i = obs.options().dtype(at::kInt);
+  return {at::empty({obs.size(0), obs.size(1), n}, o), at::empty({obs.size(0), obs.size(1), n}, o),
+          at::empty({obs.size(0)}, o), at::empty({obs.size(0)}, i), at::empty({obs.size(0)}, i)};
+}
 // the NLL of K candidate models per trajectory: params (K * B, P), row
 // k * B + b = candidate k of trajectory b -> nll (K, B), status (K, B)
 std::tuple<Tensor, Tensor> nll_sweep_gpu(const Tensor& obs, const Tensor& params, int64_t K,
@@ -416,6 +459,8 @@ TORCH_LIBRARY(eks, m) {
   m.def("smooth(Tensor obs, Tensor params, int n, int r, str mode, int flags, int algo) -> "
         "(Tensor, Tensor)");
   m.def("smooth_var(Tensor obs, Tensor params, int n, int r) -> (Tensor, Tensor, Tensor)");
+  m.def("smooth_gaps(Tensor obs, Tensor params, int n, int r, str mode) -> "
+        "(Tensor out, Tensor var, Tensor nll, Tensor nobs, Tensor status)");
   m.def("nll(Tensor obs, Tensor params, int n, int r, str mode, int flags) -> Tensor");
   m.def("nll_sweep(Tensor obs, Tensor params, int K, int n, int r, str mode) -> (Tensor, Tensor)");
   m.def("fit(Tensor obs, str kind, int n, int r, float smooth_param, float quantile_keep, "
@@ -431,6 +476,7 @@ TORCH_LIBRARY_IMPL(eks, CUDA, m) {
   m.impl("backward", &backward_gpu);
   m.impl("smooth", &smooth_gpu);
   m.impl("smooth_var", &smooth_var_gpu);
+  m.impl("smooth_gaps", &smooth_gaps_gpu);
   m.impl("nll", &nll_gpu);
   m.impl("nll_sweep", &nll_sweep_gpu);
   m.impl("fit", &fit_gpu);
@@ -444,6 +490,7 @@ TORCH_LIBRARY_IMPL(eks, Meta, m) {
   m.impl("backward", &backward_meta);
   m.impl("smooth", &smooth_meta);
   m.impl("smooth_var", &smooth_var_meta);
+  m.impl("smooth_gaps", &smooth_gaps_meta);
   m.impl("nll", &nll_meta);
   m.impl("nll_sweep", &nll_sweep_meta);
   m.impl("fit", &fit_meta);

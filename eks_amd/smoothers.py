@@ -53,6 +53,26 @@ def _run_fused(stack: np.ndarray, model: dict, mode: str = "median", want_ms=Fal
     return out, ms, nll
 
 
+def _complete_frames(preds, ev):
+    """Frames whose ensemble average and variance are finite in every column."""
+    return np.isfinite(preds).all(axis=1) & np.isfinite(ev).all(axis=1)
+
+
+def _run_gaps(yev, model: dict, mode: str = "median", want_var=False):
+    """The hand-off planes of one keypoint through batch.smooth_gaps (columns
+    with a non-finite average or variance are missing) -> out (T, n), nll,
+    var (T, n) or None, the number of missing entries."""
+    _, T, _, n = yev.shape
+    r = len(model["m0"])
+    params = batch.pack_params(model["m0"], model["S0"], model["A"], model["Q"], model["C"],
+                               model["offset"])
+    res = batch.smooth_gaps(yev, params, n=n, r=r, mode=mode, want_var=want_var, want_nll=True,
+                            check=True)
+    return (res["out"][0].cpu().numpy(), float(res["nll"][0].item()),
+            res["var"][0].cpu().numpy() if want_var else None,
+            T * n - int(res["nobs"][0].item()))
+
+
 def _auto_smooth_param(yev, model: dict, mode: str = "median") -> float:
     """The smoothing parameter chosen by likelihood (batch.select_smooth_param)
     for one keypoint: ``model`` fitted with smooth_param = 1, ``yev`` the
@@ -65,13 +85,20 @@ def _auto_smooth_param(yev, model: dict, mode: str = "median") -> float:
 
 
 def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, smooth_param,
-                                       quantile_keep_pca, camera_names, posterior_var=False):
+                                       quantile_keep_pca, camera_names, posterior_var=False,
+                                       allow_missing=False):
     """Multi-view PCA smoother for one keypoint (eks/multiview_pca_smoother.py:611-767).
 
     ``smooth_param=None``: chosen by minimising the filter's NLL on the device
     (batch.select_smooth_param); the dict then gains 'smooth_param', and the
     frames equal those of a call with that value.
 
+    ``allow_missing=True``: a column whose ensemble average or variance is not
+    finite (a NaN prediction of any member) is a missing observation; the
+    model is fitted on the frames that are complete in every column, the
+    smoother steps over the gaps (batch.smooth_gaps) and every frame of the
+    output is finite.  The dict gains 'n_missing', the number of missing
+    entries.  It needs a ``smooth_param``.
 
     markers_list_cameras[camera][model] is a DataFrame whose first two
     columns are that camera's x and y predictions.  Returns
@@ -88,15 +115,24 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
     cols = [np.stack([np.asarray(markers_list_cameras[c][e].to_numpy()[:, :2], dtype=np.float64)
                       for e in range(n_models)]) for c in range(V)]  # V x (E, T, 2)
     stack = np.concatenate(cols, axis=2)  # (E, T, 2V), camera-major columns
+    if allow_missing and smooth_param is None:
+        raise ValueError("allow_missing=True needs a smooth_param: the likelihood sweep does "
+                         "not step over gaps")
     yev, preds, ev = core.ensemble_handoff(stack)
     auto = smooth_param is None
-    if auto:
-        smooth_param = _auto_smooth_param(
-            yev, fit.multicam_model(preds, ev, 1.0, quantile_keep_pca))
-    model = fit.multicam_model(preds, ev, smooth_param, quantile_keep_pca)
-    out, _, _, *pv = _run_fused(stack, model, yev=yev, want_var=bool(posterior_var))
-    pdindex = make_dlc_pandas_index([keypoint_ensemble])
     dfs = {}
+    if allow_missing:
+        ok = _complete_frames(preds, ev)
+        model = fit.multicam_model(preds[ok], ev[ok], smooth_param, quantile_keep_pca)
+        out, _, var, dfs["n_missing"] = _run_gaps(yev, model, want_var=bool(posterior_var))
+        pv = [var]
+    else:
+        if auto:
+            smooth_param = _auto_smooth_param(
+                yev, fit.multicam_model(preds, ev, 1.0, quantile_keep_pca))
+        model = fit.multicam_model(preds, ev, smooth_param, quantile_keep_pca)
+        out, _, _, *pv = _run_fused(stack, model, yev=yev, want_var=bool(posterior_var))
+    pdindex = make_dlc_pandas_index([keypoint_ensemble])
     if auto:
         dfs["smooth_param"] = smooth_param
     nan = np.full(out.shape[0], np.nan)
@@ -178,9 +214,15 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
 
 def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth_param,
                                          quantile_keep_pca=25, ensembling_mode="median",
-                                         posterior_var=False):
+                                         posterior_var=False, allow_missing=False):
     """Single-view EKS for one keypoint (the reference
     snapshot has no single-view smoother).
+
+    ``allow_missing=True``: a coordinate whose ensemble average or variance is
+    not finite (a NaN prediction of any member) is a missing observation; the
+    model is fitted on the complete frames, the smoother steps over the gaps
+    (batch.smooth_gaps), 'nll' is the NLL over the observed entries and the
+    dict gains 'n_missing'.  It needs a ``smooth_param``.
 
     markers_list: E DataFrames with '{keypoint}_x' / '{keypoint}_y' columns.
     Model: C = A = I2, m0 = 0, S0 = diag(var), Q = s cov(diff) over the
@@ -193,18 +235,31 @@ def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth
     keys = [f"{keypoint_ensemble}_x", f"{keypoint_ensemble}_y"]
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in keys], 1)
                       for df in markers_list])  # (E, T, 2)
+    if allow_missing and smooth_param is None:
+        raise ValueError("allow_missing=True needs a smooth_param: the likelihood sweep does "
+                         "not step over gaps")
     yev, preds, ev = core.ensemble_handoff(stack, ensembling_mode)
     auto = smooth_param is None
-    if auto:
-        smooth_param = _auto_smooth_param(
-            yev, fit.singleview_model(preds, ev, 1.0, quantile_keep_pca), ensembling_mode)
-    model = fit.singleview_model(preds, ev, smooth_param, quantile_keep_pca)
-    out, _, nll, *pv = _run_fused(stack, model, mode=ensembling_mode, want_nll=True, yev=yev,
-                                  want_var=bool(posterior_var))
+    n_missing = None
+    if allow_missing:
+        ok = _complete_frames(preds, ev)
+        model = fit.singleview_model(preds[ok], ev[ok], smooth_param, quantile_keep_pca)
+        out, nll, var, n_missing = _run_gaps(yev, model, mode=ensembling_mode,
+                                             want_var=bool(posterior_var))
+        pv = [var]
+    else:
+        if auto:
+            smooth_param = _auto_smooth_param(
+                yev, fit.singleview_model(preds, ev, 1.0, quantile_keep_pca), ensembling_mode)
+        model = fit.singleview_model(preds, ev, smooth_param, quantile_keep_pca)
+        out, _, nll, *pv = _run_fused(stack, model, mode=ensembling_mode, want_nll=True, yev=yev,
+                                      want_var=bool(posterior_var))
     nan = np.full(out.shape[0], np.nan)
     idx = make_dlc_pandas_index([keypoint_ensemble])
     df = pd.DataFrame(np.stack([out[:, 0], out[:, 1], nan], 1), columns=idx)
     res = {'markers_df': df, 'nll': nll}
+    if allow_missing:
+        res['n_missing'] = n_missing
     if auto:
         res['smooth_param'] = smooth_param
     if posterior_var:

@@ -312,6 +312,54 @@ int eks_nll_sweep(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, i
                   int32_t *status /* (K, B), required, zeroed by the call */, void *stream);
 
 /*
+ * eks_smooth_gaps -- the smoother through missing observations, time-parallel
+ * over chunks in information form.  Column (t, j) of trajectory b is MISSING
+ * iff its ensemble average or its ensemble variance is not finite (a NaN
+ * member; a +-inf member; a non-finite y or ev of a hand-off); there is no
+ * mask argument -- a caller who rejects a prediction writes NaN into it.  A
+ * missing column is left out of the update (a frame with nothing observed is
+ * a pure prediction), and out / pvar are written for EVERY (t, j), missing or
+ * not: the interpolation and its variance.  With complete data the results
+ * equal eks_smooth's / eks_smooth_var's to rounding.  Every other entry point
+ * keeps its NaN propagation.
+ *
+ *   obs      member observations, strides as eks_ensemble (EKS_F32 / EKS_F64),
+ *            or the y / ev hand-off planes of eks_fit (EKS_YEV32 / EKS_YEV64;
+ *            strides ignored)
+ *   mode     EKS_MEDIAN / EKS_MEAN (the ensemble average)
+ *   params   (B, P) f64 packed models (see eks_param_len)
+ *   out      out(b,t,j) = c_j ms_t + offset_j = out[b*ob + t*ot + j*oj] (f64); REQUIRED
+ *   pvar     pvar(b,t,j) = c_j Vs_t c_j^T with out's strides, or NULL
+ *   ms       (B, T, r) contiguous smoothed means, or NULL
+ *   Vs       (B, T, r, r) contiguous smoothed covariances, or NULL
+ *   nll      (B) the Gaussian innovation NLL over the observed entries (a frame
+ *            with nothing observed adds 0), or NULL
+ *   nobs     (B) int32 number of observed entries, or NULL
+ *   status   (B) int32, REQUIRED; zeroed by the call.  EKS_STATUS_SCAN for a
+ *            trajectory with an exact observation (an OBSERVED column with
+ *            ev[t][j] == 0: a single member or identical members), whose
+ *            outputs are NaN; EKS_STATUS_SINGULAR where S_t of the RTS gain or
+ *            I + P J of a composition is singular (finite operands only).
+ *            Other trajectories are unaffected.  A trajectory with nothing
+ *            observed at all is not an error: its output is the prior carried
+ *            forward, m_t = A^t m0.
+ * r = 2 or 3, n <= 64, E <= eks_max_members(), else EKS_ERR_UNSUPPORTED (the
+ * size queries return 0).  B = 0: EKS_OK, nothing launched.  There are no
+ * model_flags: the general model runs.  Results are bit-reproducible.
+ * eks_smooth_gaps_chunk_len: the chunk length as launched (a single chunk
+ * covering T is the sequential form); EKS_DBG_GAPS_CHUNK forces it.
+ */
+size_t eks_smooth_gaps_workspace_bytes(int64_t B, int64_t T, int n, int r);
+int64_t eks_smooth_gaps_chunk_len(int64_t B, int64_t T, int r);
+int eks_smooth_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
+                    int64_t sb, int64_t st, int64_t se, int64_t sj, int mode, const double *params,
+                    double *out, int64_t ob, int64_t ot, int64_t oj, /* REQUIRED */
+                    double *pvar /* out's strides, or NULL */, double *ms /* (B,T,r) or NULL */,
+                    double *Vs /* (B,T,r,r) or NULL */, double *nll /* (B) or NULL */,
+                    int32_t *nobs /* (B) observed entries, or NULL */, void *workspace,
+                    size_t workspace_bytes, int32_t *status, void *stream);
+
+/*
  * Time-sharded smoothing (SURVEY.md §8(e) "shard the time axis"): the frames
  * of every trajectory are split into nseg contiguous segments, segment k on
  * rank k, and the chunked scan of eks_smooth runs per segment in three
@@ -451,10 +499,12 @@ int eks_interp1d(const double *x, int64_t nx, const double *y, int64_t ncol, int
  *                          eks_smooth_var_workspace_bytes.
  *   EKS_DBG_SWEEP_CHUNK    eks_nll_sweep's chunk length, with the same rule.
  *                          Set it before eks_nll_sweep_workspace_bytes.
+ *   EKS_DBG_GAPS_CHUNK     eks_smooth_gaps's chunk length, with the same rule.
+ *                          Set it before eks_smooth_gaps_workspace_bytes.
  */
 enum { EKS_DBG_WAIT_US = 1, EKS_DBG_A3_SLICE_BYTES = 2, EKS_DBG_FIT_SELECT = 3,
        EKS_DBG_A3_MODE = 4, EKS_DBG_A3_LB = 5, EKS_DBG_RT_FORM = 6, EKS_DBG_PVAR_CHUNK = 7,
-       EKS_DBG_SWEEP_CHUNK = 8 };
+       EKS_DBG_SWEEP_CHUNK = 8, EKS_DBG_GAPS_CHUNK = 9 };
 int64_t eks_debug_set(int key, int64_t value);
 
 /*
