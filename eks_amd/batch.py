@@ -497,6 +497,64 @@ def smooth_gaps(obs, params, *, n: int, r: int, mode: str = "median", want_var: 
     return dict(out=out, var=var, Vs=Vs, ms=ms, nll=nll_, nobs=nobs, status=status)
 
 
+def nll_sweep_gaps(obs, params, *, K: int, n: int, r: int, mode: str = "median",
+                   check: bool = True, status=None, stream=None):
+    """``nll_sweep`` through missing observations (eks_nll_sweep_gaps): the
+    innovation NLL over the observed entries of K candidate models for each of
+    B trajectories in one call, with ``smooth_gaps``'s missing rule (column
+    (t, j) is missing iff its ensemble average or variance is not finite).
+    The members (or the hand-off planes) are read and reduced once for all
+    candidates; a step with a camera out or nothing observed at all needs no
+    special case.
+
+    ``params`` is (K * B, P): row k * B + b is candidate k of trajectory b.
+    The candidates of a trajectory may differ in m0, S0, A and Q; C and
+    offset must be equal.  Returns dict(nll=(K, B) float64, nobs=(B,) int32
+    observed entries, status=(K, B) int32).  A trajectory with nothing
+    observed has NLL exactly 0.0 for every candidate.  With ``check=True``
+    the call synchronises and raises ValueError on EKS_STATUS_BAD_MODEL (C or
+    offset differ between candidates) and on EKS_STATUS_SCAN (an observed
+    column with zero ensemble variance; there is no fallback path), and
+    LinAlgError on EKS_STATUS_SINGULAR."""
+    torch = _lib.require_gpu()
+    B, T, E, dt = _obs_code(obs, n)
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    yev = isinstance(obs, Yev)
+    if yev and mode != obs.mode:
+        raise ValueError("the hand-off planes were made in another averaging mode")
+    P = param_len(n, r)
+    if K < 0 or params.shape != (K * B, P) or params.dtype != torch.float64 \
+            or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous ({K * B}, {P}) float64 tensor")
+    dev = obs.device
+    out = torch.empty((K, B), dtype=torch.float64, device=dev)
+    nobs = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty((K, B), dtype=torch.int32, device=dev)
+    elif status.shape != (K, B) or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError(f"status must be a contiguous ({K}, {B}) int32 tensor")
+    lib = _lib.load()
+    ws = workspace(lib.eks_nll_sweep_gaps_workspace_bytes(B, K, T, n, r), dev,
+                   slot="nll_sweep_gaps")
+    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
+    _lib.check(lib.eks_nll_sweep_gaps(
+        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
+        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(), K,
+        out.data_ptr(), nobs.data_ptr(), ws.data_ptr(), ws.numel(), status.data_ptr(),
+        _lib.stream_ptr(stream)), "eks_nll_sweep_gaps")
+    if check and K * B > 0:
+        bits = status_bits(status)
+        if bits & _lib.EKS_STATUS_BAD_MODEL:
+            raise ValueError("the candidates of a trajectory must share C and offset")
+        if bits & _lib.EKS_STATUS_SCAN:
+            raise ValueError("an observed column with zero ensemble variance: "
+                             "eks_nll_sweep_gaps does not serve it")
+        if bits & _lib.EKS_STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+    return dict(nll=out, nobs=nobs, status=status)
+
+
 DEFAULT_SWEEP_GRID = tuple(10.0 ** e for e in range(-4, 5))
 
 
@@ -530,7 +588,7 @@ def scale_q(params, s, *, r: int):
 
 
 def select_smooth_param(obs, params, *, n: int, r: int, mode: str = "median", grid=None,
-                        refine: int = 2):
+                        refine: int = 2, allow_missing: bool = False):
     """The smoothing parameter of every trajectory chosen by likelihood on the
     device, as the reference's later versions do for ``smooth_param=None``.
 
@@ -543,8 +601,17 @@ def select_smooth_param(obs, params, *, n: int, r: int, mode: str = "median", gr
     ``refine`` = 2 rounds its spacing is 10 ** (1 / 16).  A later round
     replaces the choice only where it lowers the NLL.
 
+    ``allow_missing=True`` scores through ``nll_sweep_gaps``: the NLL over the
+    observed entries, with ``smooth_gaps``'s missing rule.  A trajectory
+    without any observation scores exactly 0 at every candidate: the tie goes
+    to the grid's smallest s, and ``at_edge`` reports it.
+
     Returns dict(smooth_param (B,), nll (B,), at_edge (B,) bool: the choice is
-    the grid's first or last point, params (B, P): the rows with Q scaled)."""
+    the grid's first or last point, params (B, P): the rows with Q scaled;
+    with ``allow_missing=True`` also nobs (B,) int32, the observed entries)."""
+    if allow_missing:
+        return _select_smooth_param_gaps(obs, params, n=n, r=r, mode=mode, grid=grid,
+                                         refine=refine)
     torch = _lib.require_gpu()
     B = params.shape[0]
     dev = params.device
@@ -571,6 +638,37 @@ def select_smooth_param(obs, params, *, n: int, r: int, mode: str = "median", gr
     at_edge = (best_s == g0[0]) | (best_s == g0[-1])
     return dict(smooth_param=best_s, nll=best_nll, at_edge=at_edge,
                 params=scale_q(params, best_s.unsqueeze(0), r=r)[0])
+
+
+def _select_smooth_param_gaps(obs, params, *, n: int, r: int, mode: str, grid, refine: int):
+    """``select_smooth_param`` with every round scored by ``nll_sweep_gaps``."""
+    torch = _lib.require_gpu()
+    B = params.shape[0]
+    dev = params.device
+    g0 = torch.as_tensor(DEFAULT_SWEEP_GRID if grid is None else np.asarray(grid, dtype=np.float64),
+                         dtype=torch.float64, device=dev)
+    if g0.dim() != 1 or g0.numel() < 1 or bool((g0[1:] <= g0[:-1]).any()) or bool((g0 <= 0).any()):
+        raise ValueError("grid must be a positive, strictly ascending 1-D sequence")
+    K = int(g0.numel())
+    g = g0.unsqueeze(0).repeat(B, 1)  # (B, K)
+    best_s = best_nll = nobs = None
+    for rnd in range(int(refine) + 1):
+        rows = scale_q(params, g.t().contiguous(), r=r)
+        res = nll_sweep_gaps(obs, rows.view(K * B, -1), K=K, n=n, r=r, mode=mode)
+        scores, nobs = res["nll"].t(), res["nobs"]  # (B, K)
+        idx = torch.argmin(scores, dim=1)  # the first minimum: the smallest s
+        s = torch.gather(g, 1, idx.unsqueeze(1))[:, 0]
+        v = torch.gather(scores, 1, idx.unsqueeze(1))[:, 0]
+        if best_s is None:
+            best_s, best_nll = s, v
+        else:
+            better = v < best_nll
+            best_s = torch.where(better, s, best_s)
+            best_nll = torch.where(better, v, best_nll)
+        g = sweep_bracket(g, idx)
+    at_edge = (best_s == g0[0]) | (best_s == g0[-1])
+    return dict(smooth_param=best_s, nll=best_nll, at_edge=at_edge,
+                params=scale_q(params, best_s.unsqueeze(0), r=r)[0], nobs=nobs)
 
 
 def status_bits(status) -> int:

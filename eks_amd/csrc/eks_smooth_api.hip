@@ -48,6 +48,7 @@ extern long long g_fit_select;  // eks_fit.hip
 extern long long g_pvar_chunk;  // eks_postvar.hip
 extern long long g_sweep_chunk;  // eks_sweep.hip
 extern long long g_gaps_chunk;   // eks_gaps.hip
+extern long long g_gaps_sweep_chunk;  // eks_gaps_sweep.hip
 }
 
 extern "C" {
@@ -272,6 +273,11 @@ int64_t eks_debug_set(int key, int64_t value) {
     case EKS_DBG_GAPS_CHUNK: {
       const long long prev = g_gaps_chunk;
       g_gaps_chunk = value > 0 ? value : 0;
+      return prev;
+    }
+    case EKS_DBG_GAPS_SWEEP_CHUNK: {
+      const long long prev = g_gaps_sweep_chunk;
+      g_gaps_sweep_chunk = value > 0 ? value : 0;
       return prev;
     }
     default: return set_err(EKS_ERR_ARG, "eks_debug_set: unknown key %d", key), -1;

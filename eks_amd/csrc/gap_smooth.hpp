@@ -370,6 +370,62 @@ struct GapMap {
   }
 };
 
+// The information-form sums of step t over its observed columns: W_t (both
+// triangles), w_t, kappa_t; `count` gains the observed entries, `exact` is set
+// by an observed ev == 0 and, once set, makes the sums NaN.
+template <int R, typename T, int E>
+EKS_DEV void gp_step_sums(const typename yev_y<T>::type *ob, const double *evp, long long t,
+                          long long B, unsigned b, int n, long long st, long long se,
+                          long long sj, int Ert, bool median, const double *Cm,
+                          const double *off, double (&W)[R][R], double (&w)[R], double &kappa,
+                          int &count, bool &exact) {
+  constexpr bool kYev = is_yev<T>::value;
+  using MT = typename yev_y<T>::type;
+  kappa = 0.0;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    w[i] = 0.0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) W[i][k] = 0.0;
+  }
+  for (int j = 0; j < n; ++j) {
+    double avg, var;
+    if constexpr (kYev) {
+      avg = (double)pl(ob, t * n + j, B, b);
+      var = pl(evp, t * n + j, B, b);
+    } else {
+      column_reduce<E, MT>(ob + t * st + j * sj, se, Ert, median, avg, var);
+    }
+    const bool seen = fabs(avg) < __builtin_inf() && fabs(var) < __builtin_inf();
+    if (!seen) continue;
+    ++count;
+    exact = exact || (var == 0.0);
+    const double z = avg - off[j];
+    const double inv = 1.0 / var;
+    kappa += kLog2Pi + log(var) + z * z * inv;
+    double cr[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) cr[i] = Cm[j * R + i];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const double ci = cr[i] * inv;
+      w[i] = fma(ci, z, w[i]);
+#pragma unroll
+      for (int k = i; k < R; ++k) W[i][k] = fma(ci, cr[k], W[i][k]);
+    }
+  }
+  if (exact) {  // an infinite W_t: the trajectory is NaN from here on, both ways
+    kappa = __builtin_nan("");
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      w[i] = __builtin_nan("");
+#pragma unroll
+      for (int k = i; k < R; ++k) W[i][k] = __builtin_nan("");
+    }
+  }
+  pv_mirror<R>(W);
+}
+
 // ===========================================================================
 // G1: W_t, w_t, kappa_t planes, the observed count and the chunk's element
 // T: float / double members, or YevIn<float / double> (the y / ev planes; E unused)
@@ -415,49 +471,9 @@ __global__ __launch_bounds__(kBlock) void k_gp_elem(GpArgs a, GpPlan p) {
     }
   }
   for (long long t = s; t < e; ++t) {
-    double W[R][R], w[R], kappa = 0.0;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      w[i] = 0.0;
-#pragma unroll
-      for (int k = 0; k < R; ++k) W[i][k] = 0.0;
-    }
-    for (int j = 0; j < n; ++j) {
-      double avg, var;
-      if constexpr (kYev) {
-        avg = (double)pl(ob, t * n + j, B, b);
-        var = pl(evp, t * n + j, B, b);
-      } else {
-        column_reduce<E, MT>(ob + t * a.st + j * a.sj, a.se, a.E, median, avg, var);
-      }
-      const bool seen = fabs(avg) < __builtin_inf() && fabs(var) < __builtin_inf();
-      if (!seen) continue;
-      ++count;
-      exact = exact || (var == 0.0);
-      const double z = avg - off[j];
-      const double inv = 1.0 / var;
-      kappa += kLog2Pi + log(var) + z * z * inv;
-      double cr[R];
-#pragma unroll
-      for (int i = 0; i < R; ++i) cr[i] = Cm[j * R + i];
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        const double ci = cr[i] * inv;
-        w[i] = fma(ci, z, w[i]);
-#pragma unroll
-        for (int k = i; k < R; ++k) W[i][k] = fma(ci, cr[k], W[i][k]);
-      }
-    }
-    if (exact) {  // an infinite W_t: the trajectory is NaN from here on, both ways
-      kappa = __builtin_nan("");
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        w[i] = __builtin_nan("");
-#pragma unroll
-        for (int k = i; k < R; ++k) W[i][k] = __builtin_nan("");
-      }
-    }
-    pv_mirror<R>(W);
+    double W[R][R], w[R], kappa;
+    gp_step_sums<R, T, E>(ob, evp, t, B, b, n, a.st, a.se, a.sj, a.E, median, Cm, off, W, w, kappa,
+                          count, exact);
     pv_store_sym<R>(wbuf, t * S, B, b, W);
     gp_store_vec<R>(swbuf, t * R, B, b, w);
     pl(kbuf, t, B, b) = kappa;
@@ -478,37 +494,39 @@ EKS_DEV void gp_store_state(double *sin, long long c, long long B, unsigned b, c
   pv_store_sym<R>(sin, c * SL + R, B, b, X.Cb);
 }
 
+// (eb, sin: the element and entering-state planes of B values, trajectories
+// here and rows in gap_sweep.hpp; false: a singular composition)
 template <int R>
-__global__ __launch_bounds__(64) void k_gp_fscan(GpArgs a, GpPlan p) {
-  const long long bl = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (bl >= a.B) return;
-  const unsigned b = (unsigned)bl;
-  const long long B = a.B;
-  const double *eb = (const double *)(a.ws + p.elem_off);
-  double *sin = (double *)(a.ws + p.sin_off);
+EKS_DEV bool gp_fscan_lane(const double *eb, double *sin, long long B, long long NC, unsigned b) {
   bool ok = true;
   Elem<R> X;
   gp_load_elem<R>(eb, 0, B, b, X);
-  for (long long c = 1; c < p.NC; ++c) {
+  for (long long c = 1; c < NC; ++c) {
     gp_store_state<R>(sin, c, B, b, X);
-    if (c + 1 == p.NC) break;
+    if (c + 1 == NC) break;
     Elem<R> e, t;
     gp_load_elem<R>(eb, c, B, b, e);
     ok = compose_elem<R>(X, e, t) && ok;
     X = t;
   }
+  return ok;
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void k_gp_fscan(GpArgs a, GpPlan p) {
+  const long long bl = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (bl >= a.B) return;
+  const unsigned b = (unsigned)bl;
+  const bool ok = gp_fscan_lane<R>((const double *)(a.ws + p.elem_off),
+                                   (double *)(a.ws + p.sin_off), a.B, p.NC, b);
   if (!ok) flag(a.status, b, EKS_STATUS_SINGULAR);
 }
 
 // ... or one wave per trajectory: lane l folds chunks [l q, (l+1) q), a
 // 64-lane shuffle scan gives the prefix before its run, and it rewrites the run
 template <int R>
-__global__ __launch_bounds__(64) void k_gp_fscan_w(GpArgs a, GpPlan p) {
-  const unsigned b = blockIdx.x;
-  const int lane = threadIdx.x;
-  const long long B = a.B, NC = p.NC;
-  const double *eb = (const double *)(a.ws + p.elem_off);
-  double *sin = (double *)(a.ws + p.sin_off);
+EKS_DEV bool gp_fscan_wave(const double *eb, double *sin, long long B, long long NC, unsigned b,
+                           int lane) {
   const long long q = (NC + 63) / 64;
   const long long c0 = min(NC, lane * q), c1 = min(NC, c0 + q);
   bool ok = true;
@@ -539,6 +557,14 @@ __global__ __launch_bounds__(64) void k_gp_fscan_w(GpArgs a, GpPlan p) {
     ok = compose_elem<R>(X, e, t) && ok;
     X = t;
   }
+  return ok;
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void k_gp_fscan_w(GpArgs a, GpPlan p) {
+  const unsigned b = blockIdx.x;
+  const bool ok = gp_fscan_wave<R>((const double *)(a.ws + p.elem_off),
+                                   (double *)(a.ws + p.sin_off), a.B, p.NC, b, threadIdx.x);
   if (!ok) flag(a.status, b, EKS_STATUS_SINGULAR);
 }
 

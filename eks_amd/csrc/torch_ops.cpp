@@ -19,6 +19,7 @@
 //   eks::smooth_var(obs, params, n, r)             posterior variances of smooth's output
 //   eks::smooth_gaps(obs, params, n, r, mode)      the smoother through missing observations
 //   eks::nll_sweep(obs, params, K, n, r, mode)     the NLL of K candidate models per trajectory
+//   eks::nll_sweep_gaps(obs, params, K, n, r, mode)  the same through missing observations
 //   eks::fit(obs, kind, n, r, s, q, mode)          eks/multiview_pca_smoother.py:684-731
 //   eks::newton_filter(y, ev, mu0, S0, A, Bm, E, max_iter)  eks/newton_eks.py:115-148
 //   eks::interp1d(x, y, xq)                        eks/multiview_pca_smoother.py:86-96
@@ -343,6 +344,42 @@ std::tuple<Tensor, Tensor> nll_sweep_meta(const Tensor& obs, const Tensor&, int6
   return {at::empty({K, obs.size(0)}, obs.options().dtype(at::kDouble)),
           at::empty({K, obs.size(0)}, obs.options().dtype(at::kInt))};
 }
+// nll_sweep through missing observations (eks_nll_sweep_gaps): the NLL over
+// the observed entries -> nll (K, B), nobs (B), status (K, B)
+std::tuple<Tensor, Tensor, Tensor> nll_sweep_gaps_gpu(const Tensor& obs, const Tensor& params,
+                                                      int64_t K, int64_t n, int64_t r,
+                                                      const std::string& mode) {
+  need_gpu(obs, "obs");
+  need_gpu(params, "params");
+  TORCH_CHECK(params.device() == obs.device(), "params is on ", params.device().str(),
+              ", obs on ", obs.device().str());
+  TORCH_CHECK(obs.dim() == 4 && obs.size(3) == n, "obs must be viewed as (B, T, E, n) with n=", n);
+  TORCH_CHECK(K >= 0, "K must be >= 0");
+  const c10::DeviceGuard g(obs.device());
+  const int64_t B = obs.size(0), T = obs.size(1), E = obs.size(2);
+  Tensor prm = params.contiguous();
+  TORCH_CHECK(prm.scalar_type() == at::kDouble && prm.dim() == 2 && prm.size(0) == K * B &&
+                  prm.size(1) == eks_param_len((int)n, (int)r),
+              "params must be a (", K * B, ", ", eks_param_len((int)n, (int)r), ") float64 tensor");
+  Tensor nll = at::empty({K, B}, f64(obs));
+  Tensor nobs = at::zeros({B}, i32(obs));
+  Tensor status = at::zeros({K, B}, i32(obs));
+  const size_t wsb = eks_nll_sweep_gaps_workspace_bytes(B, K, T, (int)n, (int)r);
+  Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 1)}, obs.options().dtype(at::kByte));
+  check(eks_nll_sweep_gaps(obs.data_ptr(), obs_dtype(obs), B, T, (int)E, (int)n, (int)r,
+                           obs.stride(0), obs.stride(1), obs.stride(2), obs.stride(3),
+                           mode_code(mode), prm.data_ptr<double>(), K, nll.data_ptr<double>(),
+                           nobs.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(),
+                           status.data_ptr<int32_t>(), cur_stream(obs)),
+        "eks_nll_sweep_gaps");
+  return {nll, nobs, status};
+}
+std::tuple<Tensor, Tensor, Tensor> nll_sweep_gaps_meta(const Tensor& obs, const Tensor&, int64_t K,
+                                                       int64_t, int64_t, const std::string&) {
+  return {at::empty({K, obs.size(0)}, obs.options().dtype(at::kDouble)),
+          at::empty({obs.size(0)}, obs.options().dtype(at::kInt)),
+          at::empty({K, obs.size(0)}, obs.options().dtype(at::kInt))};
+}
 // compute_nll: the filter-only pass; raises where the reference's solve would
 // (singular system) or when a model promise does not hold
 Tensor nll_gpu(const Tensor& obs, const Tensor& params, int64_t n, int64_t r,
@@ -463,6 +500,8 @@ TORCH_LIBRARY(eks, m) {
         "(Tensor out, Tensor var, Tensor nll, Tensor nobs, Tensor status)");
   m.def("nll(Tensor obs, Tensor params, int n, int r, str mode, int flags) -> Tensor");
   m.def("nll_sweep(Tensor obs, Tensor params, int K, int n, int r, str mode) -> (Tensor, Tensor)");
+  m.def("nll_sweep_gaps(Tensor obs, Tensor params, int K, int n, int r, str mode) -> "
+        "(Tensor, Tensor, Tensor)");
   m.def("fit(Tensor obs, str kind, int n, int r, float smooth_param, float quantile_keep, "
         "str mode) -> (Tensor, Tensor)");
   m.def("newton_filter(Tensor y, Tensor ev, Tensor mu0, Tensor S0, Tensor A, Tensor Bm, "
@@ -479,6 +518,7 @@ TORCH_LIBRARY_IMPL(eks, CUDA, m) {
   m.impl("smooth_gaps", &smooth_gaps_gpu);
   m.impl("nll", &nll_gpu);
   m.impl("nll_sweep", &nll_sweep_gpu);
+  m.impl("nll_sweep_gaps", &nll_sweep_gaps_gpu);
   m.impl("fit", &fit_gpu);
   m.impl("newton_filter", &newton_gpu);
   m.impl("interp1d", &interp_gpu);
@@ -493,6 +533,7 @@ TORCH_LIBRARY_IMPL(eks, Meta, m) {
   m.impl("smooth_gaps", &smooth_gaps_meta);
   m.impl("nll", &nll_meta);
   m.impl("nll_sweep", &nll_sweep_meta);
+  m.impl("nll_sweep_gaps", &nll_sweep_gaps_meta);
   m.impl("fit", &fit_meta);
   m.impl("newton_filter", &newton_meta);
   m.impl("interp1d", &interp_meta);

@@ -23,6 +23,8 @@ CPU tensor is a dispatch error).  Layout conventions are those of
                variances diag(C Vs C^T) of smooth's output and the smoothed covariances
     nll_sweep  (obs, params (K*B, P), K, n, r, mode) -> (nll (K,B), status (K,B)): the NLL
                of K candidate models per trajectory, the members reduced once
+    nll_sweep_gaps (obs, params (K*B, P), K, n, r, mode) -> (nll (K,B), nobs (B), status (K,B)):
+               nll_sweep through missing observations, the NLL over the observed entries
     smooth_gaps (obs, params, n, r, mode) -> (out, var (B,T,n), nll (B), nobs (B), status):
                the smoother through missing observations (non-finite ensemble average
                or variance), its posterior variances and the NLL over the observed entries
@@ -38,7 +40,7 @@ from . import _lib
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libeks_torch.so")
 
 OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "smooth_gaps", "nll",
-       "nll_sweep", "fit", "newton_filter", "interp1d")
+       "nll_sweep", "nll_sweep_gaps", "fit", "newton_filter", "interp1d")
 
 
 def _load():

@@ -144,9 +144,31 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
     return dfs
 
 
+def _run_gaps_pupil(yev, model: dict, pv: bool):
+    """The pupil hand-off planes through batch.smooth_gaps -> out (T, 8),
+    ms (T, 3), var (T, 8) and Vs (T, 3, 3) (None unless ``pv``), the number of
+    missing entries."""
+    _, T, _, n = yev.shape
+    params = batch.pack_params(model["m0"], model["S0"], model["A"], model["Q"], model["C"],
+                               model["offset"])
+    res = batch.smooth_gaps(yev, params, n=n, r=3, want_ms=True, want_var=pv, want_Vs=pv,
+                            check=True)
+    return (res["out"][0].cpu().numpy(), res["ms"][0].cpu().numpy(),
+            res["var"][0].cpu().numpy() if pv else None,
+            res["Vs"][0].cpu().numpy() if pv else None, T * n - int(res["nobs"][0].item()))
+
+
 def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
-                                   state_transition_matrix, posterior_var=False):
+                                   state_transition_matrix, posterior_var=False,
+                                   allow_missing=False):
     """IBL pupil smoother (eks/pupil_smoother.py:82-223).
+
+    ``allow_missing=True``: a column whose ensemble average or variance is not
+    finite (a NaN prediction of any member: a blink) is a missing observation;
+    the model is fitted on the frames that are complete in every column, the
+    smoother steps over the gaps (batch.smooth_gaps) and every frame of the
+    output is finite.  The dict gains 'n_missing', the number of missing
+    entries.
 
     Returns {'markers_df': smoothed keypoints in the order top, right, bottom,
     left (NaN likelihood), 'latents_df': diameter, com_x, com_y}.  With
@@ -154,10 +176,16 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
     the posterior variances) and 'latents_posterior_var_df' (diag(Vs))."""
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
-    yev, preds, _ = core.ensemble_handoff(stack)
-    model = fit.pupil_model(preds, state_transition_matrix)
+    yev, preds, ev = core.ensemble_handoff(stack)
     pv = bool(posterior_var)
-    out, ms, _, *var_Vs = _run_fused(stack, model, want_ms=True, yev=yev, want_var=pv, want_Vs=pv)
+    n_missing = None
+    if allow_missing:
+        model = fit.pupil_model(preds[_complete_frames(preds, ev)], state_transition_matrix)
+        out, ms, *var_Vs, n_missing = _run_gaps_pupil(yev, model, pv)
+    else:
+        model = fit.pupil_model(preds, state_transition_matrix)
+        out, ms, _, *var_Vs = _run_fused(stack, model, want_ms=True, yev=yev, want_var=pv,
+                                         want_Vs=pv)
     nan = np.full(out.shape[0], np.nan)
 
     def markers(arr):
@@ -171,6 +199,8 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
     idx = pd.MultiIndex.from_arrays([[tracker_name] * 3, ['diameter', 'com_x', 'com_y']],
                                     names=('scorer', 'latent'))
     res = {'markers_df': markers(out), 'latents_df': pd.DataFrame(lat, columns=idx)}
+    if allow_missing:
+        res['n_missing'] = n_missing
     if pv:
         var, Vs = var_Vs
         res['posterior_var_df'] = markers(var)
@@ -180,7 +210,7 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
 
 
 def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s_grid,
-                          com_s_grid):
+                          com_s_grid, allow_missing=False):
     """The pupil smoother with its smoothing parameters chosen by likelihood.
 
     Every (diameter_s, com_s) pair of the grid defines a model
@@ -189,11 +219,33 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
     predictions are shared, batch stride 0) by their innovation NLL, and the
     argmin is smoothed.  Returns ensemble_kalman_smoother_pupil's dict plus
     'nll' (len(diameter_s_grid), len(com_s_grid)) and 'best' (d, c).
-    (The reference has no NLL loop: SURVEY.md §0; this is the build's.)"""
+    (The reference has no NLL loop: SURVEY.md §0; this is the build's.)
+
+    ``allow_missing=True``: the candidates are fitted on the complete frames
+    (they share C and offset and differ in A and Q), scored over the observed
+    entries in one batch.nll_sweep_gaps call, and the argmin is smoothed
+    through the gaps (ensemble_kalman_smoother_pupil(allow_missing=True))."""
     torch = _lib.require_gpu()
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
     E, T, n = stack.shape
+    if allow_missing:
+        yev, preds, ev = core.ensemble_handoff(stack)
+        ok = _complete_frames(preds, ev)
+        grid = [(d, c) for d in diameter_s_grid for c in com_s_grid]
+        models = [fit.pupil_model(preds[ok], np.diag([d, c, c])) for d, c in grid]
+        stackp = lambda k: np.stack([m[k] for m in models])  # noqa: E731
+        params = batch.pack_params(stackp("m0"), stackp("S0"), stackp("A"), stackp("Q"),
+                                   stackp("C"), stackp("offset"))
+        scores = batch.nll_sweep_gaps(yev, params, K=len(grid), n=n, r=3)["nll"][:, 0]
+        scores = scores.cpu().numpy()
+        best = grid[int(np.argmin(scores))]
+        res = ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
+                                             np.diag([best[0], best[1], best[1]]),
+                                             allow_missing=True)
+        res["nll"] = scores.reshape(len(diameter_s_grid), len(com_s_grid))
+        res["best"] = best
+        return res
     preds, _ = core.ensemble_array(stack)
     grid = [(d, c) for d in diameter_s_grid for c in com_s_grid]
     models = [fit.pupil_model(preds, np.diag([d, c, c])) for d, c in grid]

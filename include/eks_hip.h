@@ -360,6 +360,49 @@ int eks_smooth_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E,
                     size_t workspace_bytes, int32_t *status, void *stream);
 
 /*
+ * eks_nll_sweep_gaps -- eks_nll_sweep through missing observations: the
+ * Gaussian innovation NLL over the OBSERVED entries (eks_smooth_gaps's nll and
+ * its missing rule: column (t, j) is missing iff its ensemble average or
+ * variance is not finite) of K candidate models for each of B trajectories in
+ * one call.  The members are read and reduced once for all candidates, to the
+ * information-form sums W_t, w_t, kappa_t (r (r + 1) / 2 + r + 1 doubles per
+ * step), which may be rank-deficient (a camera out) or zero (a blink); a
+ * candidate costs r x r work per step whatever n is.
+ *
+ *   obs      member observations, strides as eks_ensemble (EKS_F32 / EKS_F64),
+ *            or the y / ev hand-off planes of eks_fit (EKS_YEV32 / EKS_YEV64;
+ *            strides ignored)
+ *   params   (K * B, P) f64 packed models (see eks_param_len): row k * B + b
+ *            is candidate k of trajectory b.  The candidates of a trajectory
+ *            may differ in m0, S0, A and Q; C and offset must equal
+ *            candidate 0's bit for bit.
+ *   nll      (K, B) f64, REQUIRED.  A trajectory with nothing observed has
+ *            exactly 0.0 for every candidate.
+ *   nobs     (B) int32 number of observed entries, or NULL
+ *   status   (K, B) int32, REQUIRED; zeroed by the call.  EKS_STATUS_SCAN on
+ *            every candidate of a trajectory with an exact observation (an
+ *            OBSERVED column with ev[t][j] == 0), whose NLLs are NaN: there is
+ *            no fallback, mark the column missing or widen its variance.
+ *            EKS_STATUS_BAD_MODEL on a row whose C or offset differ from
+ *            candidate 0's (that row only); EKS_STATUS_SINGULAR where I + P W
+ *            of a step or I + P J of a composition is singular (finite
+ *            operands only).  Other trajectories are unaffected.
+ * r = 2 or 3, n <= 64, E <= eks_max_members(), K * B <= 2^28, else
+ * EKS_ERR_UNSUPPORTED (the size queries return 0).  B = 0 or K = 0: EKS_OK,
+ * nothing launched.  Results are bit-reproducible.
+ * eks_nll_sweep_gaps_chunk_len: the chunk length as launched (a single chunk
+ * covering T is the sequential form); EKS_DBG_GAPS_SWEEP_CHUNK forces it.
+ */
+size_t eks_nll_sweep_gaps_workspace_bytes(int64_t B, int64_t K, int64_t T, int n, int r);
+int64_t eks_nll_sweep_gaps_chunk_len(int64_t B, int64_t K, int64_t T, int r);
+int eks_nll_sweep_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
+                       int64_t sb, int64_t st, int64_t se, int64_t sj, int mode,
+                       const double *params /* (K*B, P): row k*B+b = candidate k of trajectory b */,
+                       int64_t K, double *nll /* (K, B) */, int32_t *nobs /* (B) or NULL */,
+                       void *workspace, size_t workspace_bytes,
+                       int32_t *status /* (K, B), required, zeroed by the call */, void *stream);
+
+/*
  * Time-sharded smoothing (SURVEY.md §8(e) "shard the time axis"): the frames
  * of every trajectory are split into nseg contiguous segments, segment k on
  * rank k, and the chunked scan of eks_smooth runs per segment in three
@@ -501,10 +544,13 @@ int eks_interp1d(const double *x, int64_t nx, const double *y, int64_t ncol, int
  *                          Set it before eks_nll_sweep_workspace_bytes.
  *   EKS_DBG_GAPS_CHUNK     eks_smooth_gaps's chunk length, with the same rule.
  *                          Set it before eks_smooth_gaps_workspace_bytes.
+ *   EKS_DBG_GAPS_SWEEP_CHUNK  eks_nll_sweep_gaps's chunk length, with the same
+ *                          rule.  Set it before
+ *                          eks_nll_sweep_gaps_workspace_bytes.
  */
 enum { EKS_DBG_WAIT_US = 1, EKS_DBG_A3_SLICE_BYTES = 2, EKS_DBG_FIT_SELECT = 3,
        EKS_DBG_A3_MODE = 4, EKS_DBG_A3_LB = 5, EKS_DBG_RT_FORM = 6, EKS_DBG_PVAR_CHUNK = 7,
-       EKS_DBG_SWEEP_CHUNK = 8, EKS_DBG_GAPS_CHUNK = 9 };
+       EKS_DBG_SWEEP_CHUNK = 8, EKS_DBG_GAPS_CHUNK = 9, EKS_DBG_GAPS_SWEEP_CHUNK = 10 };
 int64_t eks_debug_set(int key, int64_t value);
 
 /*
