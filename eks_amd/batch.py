@@ -352,6 +352,71 @@ def fit(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_keep: f
     return params, status
 
 
+def fit_gaps(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_keep: float,
+             mode: str = "median", check: bool = True, params=None, status=None, keep_yev=None):
+    """``fit`` through missing observations (eks_fit_gaps).  A frame of a
+    trajectory is complete iff the ensemble average and variance of all n
+    columns are finite (``smooth_gaps``'s missing rule, per frame); the
+    percentile is taken over the complete frames, the kept frames are the
+    complete ones at or below it, and the model is ``fit``'s over the kept
+    frames in frame order -- the host fit on ``preds[ok], ev[ok]``.
+
+    Returns dict(params (B, P) float64, status (B,) int32, yev: the ``Yev``
+    hand-off planes ``smooth_gaps`` / ``nll_sweep_gaps`` read in place of the
+    members (the one passed as ``keep_yev`` when it is large enough),
+    ncomplete (B,) int32 complete frames, nkept (B,) int32 kept frames).
+    With ``check=True`` the call synchronises and raises ValueError when a
+    trajectory has no complete frame (EKS_STATUS_SINGULAR in ``status``);
+    ``check=False`` leaves ``status`` to the caller."""
+    torch = _lib.require_gpu()
+    if obs.dim() != 4 or obs.shape[3] != n:
+        raise ValueError("obs must be viewed as (B, T, E, n)")
+    B, T, E, _ = obs.shape
+    if obs.dtype not in (torch.float32, torch.float64):
+        raise TypeError("obs must be float32 or float64")
+    dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    k = {"singleview": _lib.EKS_FIT_SINGLEVIEW, "multicam": _lib.EKS_FIT_MULTICAM}[kind]
+    lib = _lib.load()
+    dev = obs.device
+    if params is None:
+        params = torch.empty((B, param_len(n, r)), dtype=torch.float64, device=dev)
+    elif params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
+            or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    elif status.shape != (B,) or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError(f"status must be a contiguous ({B},) int32 tensor")
+    ncomplete = torch.empty((B,), dtype=torch.int32, device=dev)
+    nkept = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws = workspace(lib.eks_fit_gaps_workspace_bytes(B, T, n), dev, slot="fit_gaps")
+    sb, st, se, sj = obs.stride()
+    m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
+    nbytes = lib.eks_yev_bytes(B, T, n, dt, E, m)
+    code = lib.eks_yev_dtype(dt, E, m)
+    if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
+        yev = keep_yev  # the buffer is reused; a Yev of another shape gets a new header
+        if (yev.shape, yev.code, yev.mode) != ((B, T, E, n), code, mode):
+            yev = Yev(keep_yev.buf, B, T, E, n, code, mode)
+    else:
+        yev = Yev(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), B, T, E, n, code,
+                  mode)
+    _lib.check(lib.eks_fit_gaps(obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj, m, k,
+                                float(smooth_param), float(quantile_keep), params.data_ptr(),
+                                ws.data_ptr(), ws.numel(), status.data_ptr(), yev.buf.data_ptr(),
+                                ncomplete.data_ptr(), nkept.data_ptr(), _lib.stream_ptr()),
+               "eks_fit_gaps")
+    if check and B > 0:
+        bad = int((ncomplete == 0).sum().item())
+        if bad:
+            raise ValueError(f"eks_fit_gaps: {bad} of {B} trajectories have no complete frame")
+        if bool((status != 0).any()):
+            raise ValueError("eks_fit_gaps: no frame was kept")
+    return dict(params=params, status=status, yev=yev, ncomplete=ncomplete, nkept=nkept)
+
+
 def nll(obs, params, *, n: int, r: int, mode: str = "median", flags: int = 0, algo: int = 0,
         check: bool = True, status=None):
     """Filter-only pass: the innovation NLL of every

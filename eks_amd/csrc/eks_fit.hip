@@ -22,6 +22,9 @@
 //                 IEEE bit patterns (12-bit digits, LDS histograms, early
 //                 exit once the candidate is unique), then numpy's linear
 //                 interpolation -> threshold, and the kept-frame bit mask
+//   k_fit_select_gaps  eks_fit_gaps' selection: the same over the complete
+//                 frames of each row (ranks from the row's own count), the
+//                 mask, the counts and a shift K from a complete frame
 //   k_fit_accum   one lane per (trajectory, chunk): ensemble again (or the y
 //                 hand-off plane + the frame mask), keep frames with
 //                 v_t <= threshold, chunk sums of y - K and its outer
@@ -708,6 +711,138 @@ __global__ __launch_bounds__(BLK, KPT > 0 ? EKS_SEL_KPT_WPE : EKS_SEL_WPE) void 
       if (first_active_lane()) krow[i >> 6] = m;
     });
   }
+}
+
+// ---------------------------------------------------------------------------
+// The selection of eks_fit_gaps: the percentile over the COMPLETE frames of
+// each row.  k_fit_worst / k_fitw_worst mark a frame that is not complete in
+// the worst plane itself: NaN (either sign) when a variance is NaN, +inf when
+// one overflows -- every key whose exponent field is all ones.  Variances
+// are >= 0, so as unsigned 64-bit integers all of those keys lie above every
+// finite variance and the M complete frames hold the ranks 0 .. M - 1 of the
+// whole row: the order statistics are selected over the row as it stands
+// (block_select over all 64 bits, nothing rewritten), and only the ranks
+// depend on M -- lo, hi and the weight g of numpy's linear rule are derived
+// here per row, where eks_fit derives them once on the host from T.
+// One block per row, every pass over the row in global memory (L2):
+//   1  M and the first complete frame
+//   2  v_(lo) by MSD radix select (12-bit digits, early exit), v_(lo+1) as the
+//      least key above it unless v_(lo) repeats, numpy's _lerp -> thr[b]
+//   3  the kept-frame mask words (complete && v <= thr: thr is finite, so the
+//      comparison is false for NaN and +inf) and their population count
+// and the shift K of the accumulation: k_fit_worst wrote frame 0's ensemble
+// average, which is NaN when frame 0 is missing and would poison every sum,
+// so such a row takes its first complete frame's average from the y plane
+// (a row whose frame 0 is complete keeps K untouched: on members without gaps
+// the fit is bit-identical to eks_fit's).  M = 0: NaN threshold, empty mask,
+// K = 0 (nothing is summed; k_fit_final reports EKS_STATUS_SINGULAR).
+// Few long rows leave most of the chip idle here (no split form as k_sel_*).
+// ---------------------------------------------------------------------------
+template <int BLK>
+__global__ __launch_bounds__(BLK) void k_fit_select_gaps(const double *__restrict__ worst,
+                                                         long long TT, double qf,
+                                                         double *__restrict__ thr,
+                                                         uint64_t *__restrict__ kept, long long W,
+                                                         const void *__restrict__ yplane, int y32,
+                                                         long long B, int n, FitShift ks,
+                                                         int32_t *__restrict__ ncomplete,
+                                                         int32_t *__restrict__ nkept) {
+  __shared__ unsigned hist[kBins];
+  __shared__ uint64_t su[4];
+  __shared__ long long si[2 + BLK / 64];
+  __shared__ unsigned long long s_cnt, s_first;
+  __shared__ double sthr;
+  constexpr uint64_t kExpAll = 0x7ff0000000000000ull;
+  const long long b = blockIdx.x;
+  const uint64_t *keys = reinterpret_cast<const uint64_t *>(worst + b * TT);
+  uint64_t *krow = kept + b * W;
+  if (threadIdx.x == 0) {
+    s_cnt = 0;
+    s_first = ~0ull;
+  }
+  __syncthreads();
+  // pass 1: the complete frames and the first of them
+  {
+    unsigned long long c = 0, f = ~0ull;
+    for_keys<BLK, kSelRowU>(keys, TT, [&](uint64_t x, long long i) {
+      if ((x & kExpAll) != kExpAll) {
+        ++c;
+        if ((unsigned long long)i < f) f = (unsigned long long)i;
+      }
+    });
+    atomicAdd(&s_cnt, c);
+    atomicMin(&s_first, f);
+  }
+  __syncthreads();
+  const long long M = (long long)s_cnt;
+  const long long first = (long long)s_first;
+  __syncthreads();  // (s_cnt counts the kept frames below)
+  if (threadIdx.x == 0 && ncomplete) ncomplete[b] = (int32_t)M;
+  if (M == 0) {
+    if (threadIdx.x == 0) {
+      thr[b] = __builtin_nan("");
+      if (nkept) nkept[b] = 0;
+    }
+    for (int j = threadIdx.x; j < n; j += BLK) ks.K[b * n + j] = 0.0;
+    for (long long w = threadIdx.x; w < W; w += BLK) krow[w] = 0ull;
+    return;
+  }
+  if (first != 0)
+    for (int j = threadIdx.x; j < n; j += BLK) {
+      const long long o = (first * n + j) * B + b;
+      ks.K[b * n + j] = y32 ? (double)((const float *)yplane)[o] : ((const double *)yplane)[o];
+    }
+  // np.percentile 'linear' on M values: virtual index (M - 1) q / 100 (the
+  // product rounded on its own, as the host's: no fused multiply-subtract)
+  const double vi = __dmul_rn((double)(M - 1), qf);
+  const long long lo = (long long)floor(vi);
+  const long long hi = lo + 1 < M ? lo + 1 : M - 1;
+  const double g = vi - (double)lo;
+  const uint64_t ka = block_select<BLK>(keys, TT, lo, 63, 0ull, hist, su, si);
+  uint64_t kb = ka;
+  if (hi != lo) {
+    // v_(lo+1) = ka if ka repeats, else the least key above ka (a complete
+    // frame's: hi < M)
+    if (threadIdx.x == 0) {
+      su[1] = ~0ull;
+      si[0] = 0;
+    }
+    __syncthreads();
+    unsigned long long c = 0, ab = ~0ull;
+    for_keys<BLK, kSelRowU>(keys, TT, [&](uint64_t x, long long) {
+      c += x <= ka;
+      if (x > ka && x < ab) ab = x;
+    });
+    atomicAdd((unsigned long long *)&si[0], c);
+    atomicMin((unsigned long long *)&su[1], ab);
+    __syncthreads();
+    kb = si[0] >= hi + 1 ? ka : su[1];
+  }
+  if (threadIdx.x == 0) {
+    const double a = __longlong_as_double((long long)ka);
+    const double bb = __longlong_as_double((long long)kb);
+    const double d = bb - a;  // numpy's _lerp
+    const double t = g >= 0.5 ? bb - d * (1.0 - g) : a + d * g;
+    thr[b] = t;
+    sthr = t;
+    s_cnt = 0;
+  }
+  __syncthreads();
+  const double th = sthr;
+  // pass 3: one ballot per wave and 64 frames is one mask word (for_keys: a
+  // wave never splits between the unrolled loop and the tail); the lanes past
+  // the row's end are inactive, so the ragged last word is zero-padded
+  unsigned long long nk = 0;
+  for_keys<BLK, kSelRowU>(keys, TT, [&](uint64_t x, long long i) {
+    const uint64_t m = __ballot(__longlong_as_double((long long)x) <= th);
+    if (first_active_lane()) {
+      krow[i >> 6] = m;
+      nk += (unsigned long long)__popcll(m);
+    }
+  });
+  if (nk) atomicAdd(&s_cnt, nk);
+  __syncthreads();
+  if (threadIdx.x == 0 && nkept) nkept[b] = (int32_t)s_cnt;
 }
 
 // ---------------------------------------------------------------------------
@@ -1967,8 +2102,9 @@ constexpr int kMaxObsFit = kNW;  // n of eks_fit (even; n > kMaxObs: the wide ke
 
 using namespace eks;
 
-extern "C" size_t eks_fit_workspace_bytes(int64_t B, int64_t T, int n) {
-  if (B <= 0 || T <= 0 || n < 1 || n > kMaxObsFit) return 0;
+// worst plane, thresholds, chunk partials, kept-frame mask, shifts K; with
+// `split` the split selection's histograms, row states, candidate keys + indices
+static size_t fit_ws_bytes(int64_t B, int64_t T, int n, bool split) {
   int nc;
   long long lc;
   fit_chunks(B, T, nc, lc, n);
@@ -1976,12 +2112,21 @@ extern "C" size_t eks_fit_workspace_bytes(int64_t B, int64_t T, int n) {
   const long long np = fit_partials(B, nc, n);
   const long long nc2 = (np + kMergeFan - 1) / kMergeFan;
   const long long W = (T + 63) / 64;  // frame-mask words per trajectory
-  // worst plane, thresholds, chunk partials, kept-frame mask, shifts K
   size_t bytes = (size_t)(B * T + B + B * (np + nc2) * len + B * W + B * n) * sizeof(double);
-  // split selection: histograms, row states, candidate keys + indices
-  if (sel_split_auto(B, T) || g_fit_select == 2)
+  if (split)
     bytes += (size_t)B * kSplitBins * 4 + (size_t)B * sizeof(SelRow) + (size_t)B * T * 12 + 512;
   return bytes;
+}
+
+extern "C" size_t eks_fit_workspace_bytes(int64_t B, int64_t T, int n) {
+  if (B <= 0 || T <= 0 || n < 1 || n > kMaxObsFit) return 0;
+  return fit_ws_bytes(B, T, n, sel_split_auto(B, T) || g_fit_select == 2);
+}
+
+// (the gap-aware selection is one block per row: no split buffers)
+extern "C" size_t eks_fit_gaps_workspace_bytes(int64_t B, int64_t T, int n) {
+  if (B <= 0 || T <= 0 || n < 2 || n % 2 != 0 || n > kMaxObsFit) return 0;
+  return fit_ws_bytes(B, T, n, false);
 }
 
 // y of the hand-off planes is float32 exactly when it is a member value:
@@ -2000,30 +2145,35 @@ extern "C" size_t eks_yev_bytes(int64_t B, int64_t T, int n, int obs_dtype, int 
   return yev_ev_offset(B, T, n, ys) + (size_t)B * T * n * 8;
 }
 
-extern "C" int eks_fit(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
-                       int64_t sb, int64_t st, int64_t se, int64_t sj, int mode, int kind,
-                       double smooth_param, double quantile_keep, double *params,
-                       void *workspace, size_t workspace_bytes, int32_t *status, void *yev,
-                       void *stream) {
+// eks_fit and eks_fit_gaps (`gaps`: the percentile over the complete frames
+// of each row by k_fit_select_gaps; status and yev required)
+static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, int64_t B, int64_t T,
+                   int E, int n, int r, int64_t sb, int64_t st, int64_t se, int64_t sj, int mode,
+                   int kind, double smooth_param, double quantile_keep, double *params,
+                   void *workspace, size_t workspace_bytes, int32_t *status, void *yev,
+                   int32_t *ncomplete, int32_t *nkept, void *stream) {
   clear_err();
-  if (!obs || !params || !workspace) return set_err(EKS_ERR_ARG, "eks_fit: NULL pointer");
-  if (B < 0 || T < 2 || E < 1 || n < 1) return set_err(EKS_ERR_ARG, "eks_fit: bad sizes");
+  if (!obs || !params || !workspace || (gaps && (!status || !yev)))
+    return set_err(EKS_ERR_ARG, "%s: NULL pointer", fn);
+  if (B < 0 || T < 2 || E < 1 || n < 1) return set_err(EKS_ERR_ARG, "%s: bad sizes", fn);
   if (B == 0) return EKS_OK;
-  if (E > kMaxMembers) return set_err(EKS_ERR_UNSUPPORTED, "eks_fit: E=%d > %d", E, kMaxMembers);
+  if (E > kMaxMembers) return set_err(EKS_ERR_UNSUPPORTED, "%s: E=%d > %d", fn, E, kMaxMembers);
   if (mode != EKS_MEDIAN && mode != EKS_MEAN)
     return set_err(EKS_ERR_ARG, "%d averaging not supported", mode);
   if (obs_dtype != EKS_F32 && obs_dtype != EKS_F64) return set_err(EKS_ERR_ARG, "bad dtype");
   if (kind != EKS_FIT_SINGLEVIEW && kind != EKS_FIT_MULTICAM)
-    return set_err(EKS_ERR_ARG, "eks_fit: unknown model kind %d", kind);
+    return set_err(EKS_ERR_ARG, "%s: unknown model kind %d", fn, kind);
   if (kind == EKS_FIT_SINGLEVIEW && r != n)
-    return set_err(EKS_ERR_ARG, "eks_fit: single-view model needs r == n");
+    return set_err(EKS_ERR_ARG, "%s: single-view model needs r == n", fn);
   if (kind == EKS_FIT_MULTICAM && (r > n || r < 1))
-    return set_err(EKS_ERR_ARG, "eks_fit: PCA model needs 1 <= r <= n");
+    return set_err(EKS_ERR_ARG, "%s: PCA model needs 1 <= r <= n", fn);
   if (!(quantile_keep >= 0.0 && quantile_keep <= 100.0))
-    return set_err(EKS_ERR_ARG, "eks_fit: quantile_keep must be in [0, 100]");
-  if (workspace_bytes < eks_fit_workspace_bytes(B, T, n))
-    return set_err(EKS_ERR_ARG, "eks_fit: workspace too small (%zu < %zu)", workspace_bytes,
-                   eks_fit_workspace_bytes(B, T, n));
+    return set_err(EKS_ERR_ARG, "%s: quantile_keep must be in [0, 100]", fn);
+  // (the shapes the kernels do not serve are refused below: the gaps query is 0 for them)
+  const size_t need = gaps && n % 2 == 0 && n <= kMaxObsFit ? eks_fit_gaps_workspace_bytes(B, T, n)
+                                                            : eks_fit_workspace_bytes(B, T, n);
+  if (workspace_bytes < need)
+    return set_err(EKS_ERR_ARG, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   FitShape sh{B, T, 0, 0};
   fit_chunks(B, T, sh.NC, sh.Lc, n);
@@ -2039,7 +2189,8 @@ extern "C" int eks_fit(const void *obs, int obs_dtype, int64_t B, int64_t T, int
       partB + B * (long long)((npart + kMergeFan - 1) / kMergeFan) * len);
   FitShift ks{reinterpret_cast<double *>(kept + B * W)};
   // split selection (few rows): its buffers after the shifts
-  const bool split_sel = g_fit_select == 1 ? false : g_fit_select == 2 ? true : sel_split_auto(B, T);
+  const bool split_sel =
+      gaps || g_fit_select == 1 ? false : g_fit_select == 2 ? true : sel_split_auto(B, T);
   const int G = (int)((T + kSegKeys - 1) / kSegKeys);
   char *sel_base = reinterpret_cast<char *>(
       (reinterpret_cast<uintptr_t>(ks.K + B * n) + 255) / 256 * 256);  // 16-byte loads in k_sel_bin
@@ -2069,6 +2220,19 @@ extern "C" int eks_fit(const void *obs, int obs_dtype, int64_t B, int64_t T, int
   // the order statistics, the threshold and (with the hand-off planes
   // written) the kept-frame mask k_fit_accum reads instead of the ev plane
   auto select = [&]() -> int {
+    if (gaps) {  // per-row ranks over the complete frames, the mask, the shift K
+      prof_mark(s, "k_fit_select_gaps");
+      const double qf = quantile_keep / 100.0;
+      if (T >= 65536)
+        hipLaunchKernelGGL(k_fit_select_gaps<1024>, dim3((unsigned)B), dim3(1024), 0, s, worst, T,
+                           qf, thr, kept, W, (const void *)yo.y, y32 ? 1 : 0, B, n, ks, ncomplete,
+                           nkept);
+      else
+        hipLaunchKernelGGL(k_fit_select_gaps<256>, dim3((unsigned)B), dim3(256), 0, s, worst, T,
+                           qf, thr, kept, W, (const void *)yo.y, y32 ? 1 : 0, B, n, ks, ncomplete,
+                           nkept);
+      return check_launch("k_fit_select_gaps");
+    }
     prof_mark(s, "k_fit_select");
     if (split_sel) {
       // few long rows: one block per (row, segment) in four launches
@@ -2120,10 +2284,10 @@ extern "C" int eks_fit(const void *obs, int obs_dtype, int64_t B, int64_t T, int
   // keypoint observations come in (x, y) pairs: n = 2 (single view) or 2V
   // (V cameras); the odd n are not compiled (they doubled this unit's code)
   if (n % 2 != 0 || n > kMaxObsFit)
-    return set_err(EKS_ERR_UNSUPPORTED, "eks_fit: n=%d not supported (even, <= %d)", n, kMaxObsFit);
+    return set_err(EKS_ERR_UNSUPPORTED, "%s: n=%d not supported (even, <= %d)", fn, n, kMaxObsFit);
   if (n > kMaxObs) {  // 5-8 cameras: the wide kernels (runtime n, runtime E)
     if (kind != EKS_FIT_MULTICAM || r != 3)
-      return set_err(EKS_ERR_UNSUPPORTED, "eks_fit: n=%d needs the PCA model with r = 3", n);
+      return set_err(EKS_ERR_UNSUPPORTED, "%s: n=%d needs the PCA model with r = 3", fn, n);
     auto wide_e = [&](auto tag, auto ytag, auto Ec) -> int {
       using Tp = decltype(tag);
       using YT = decltype(ytag);
@@ -2219,7 +2383,7 @@ extern "C" int eks_fit(const void *obs, int obs_dtype, int64_t B, int64_t T, int
         rc = dispatch_r(r, [&](auto Rc) {
           constexpr int RR = decltype(Rc)::value;
           if constexpr (RR > NN) {
-            return set_err(EKS_ERR_ARG, "eks_fit: r > n");
+            return set_err(EKS_ERR_ARG, "%s: r > n", fn);
           } else {
             hipLaunchKernelGGL((k_fit_final<RR, NN>), dim3((unsigned)B), dim3(64), 0, s, B, src,
                                ks, kind, smooth_param, params, status);
@@ -2239,4 +2403,24 @@ extern "C" int eks_fit(const void *obs, int obs_dtype, int64_t B, int64_t T, int
     if (y32) return by_type(float{}, float{});
     return obs_dtype == EKS_F32 ? by_type(float{}, double{}) : by_type(double{}, double{});
   });
+}
+
+extern "C" int eks_fit(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
+                       int64_t sb, int64_t st, int64_t se, int64_t sj, int mode, int kind,
+                       double smooth_param, double quantile_keep, double *params,
+                       void *workspace, size_t workspace_bytes, int32_t *status, void *yev,
+                       void *stream) {
+  return fit_run("eks_fit", false, obs, obs_dtype, B, T, E, n, r, sb, st, se, sj, mode, kind,
+                 smooth_param, quantile_keep, params, workspace, workspace_bytes, status, yev,
+                 nullptr, nullptr, stream);
+}
+
+extern "C" int eks_fit_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n,
+                            int r, int64_t sb, int64_t st, int64_t se, int64_t sj, int mode,
+                            int kind, double smooth_param, double quantile_keep, double *params,
+                            void *workspace, size_t workspace_bytes, int32_t *status, void *yev,
+                            int32_t *ncomplete, int32_t *nkept, void *stream) {
+  return fit_run("eks_fit_gaps", true, obs, obs_dtype, B, T, E, n, r, sb, st, se, sj, mode, kind,
+                 smooth_param, quantile_keep, params, workspace, workspace_bytes, status, yev,
+                 ncomplete, nkept, stream);
 }

@@ -21,6 +21,7 @@
 //   eks::nll_sweep(obs, params, K, n, r, mode)     the NLL of K candidate models per trajectory
 //   eks::nll_sweep_gaps(obs, params, K, n, r, mode)  the same through missing observations
 //   eks::fit(obs, kind, n, r, s, q, mode)          eks/multiview_pca_smoother.py:684-731
+//   eks::fit_gaps(obs, kind, n, r, s, q, mode)     the same through missing observations
 //   eks::newton_filter(y, ev, mu0, S0, A, Bm, E, max_iter)  eks/newton_eks.py:115-148
 //   eks::interp1d(x, y, xq)                        eks/multiview_pca_smoother.py:86-96
 #include <ATen/ATen.h>
@@ -429,6 +430,46 @@ std::tuple<Tensor, Tensor> fit_meta(const Tensor& obs, const std::string&, int64
           at::empty({obs.size(0)}, obs.options().dtype(at::kInt))};
 }
 
+// ---------------------------------------------------------------- fit_gaps
+// (params, status, yev bytes, ncomplete, nkept); the planes in yev have the
+// type eks_yev_dtype(obs dtype, E, mode) names
+using FitGaps = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor>;
+FitGaps fit_gaps_gpu(const Tensor& obs, const std::string& kind, int64_t n, int64_t r,
+                     double smooth_param, double quantile_keep, const std::string& mode) {
+  need_gpu(obs, "obs");
+  TORCH_CHECK(obs.dim() == 4 && obs.size(3) == n, "obs must be viewed as (B, T, E, n) with n=", n);
+  TORCH_CHECK(kind == "singleview" || kind == "multicam", "kind must be singleview or multicam");
+  const c10::DeviceGuard g(obs.device());
+  const int64_t B = obs.size(0), T = obs.size(1), E = obs.size(2);
+  Tensor params = at::empty({B, eks_param_len((int)n, (int)r)}, f64(obs));
+  Tensor status = at::empty({B}, i32(obs));
+  Tensor ncomplete = at::empty({B}, i32(obs));
+  Tensor nkept = at::empty({B}, i32(obs));
+  const size_t yb = eks_yev_bytes(B, T, (int)n, obs_dtype(obs), (int)E, mode_code(mode));
+  Tensor yev = at::empty({(int64_t)yb}, obs.options().dtype(at::kByte));
+  const size_t wsb = eks_fit_gaps_workspace_bytes(B, T, (int)n);
+  Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 1)}, obs.options().dtype(at::kByte));
+  if (B > 0)  // (an empty batch has no planes to point at)
+    check(eks_fit_gaps(obs.data_ptr(), obs_dtype(obs), B, T, (int)E, (int)n, (int)r, obs.stride(0),
+                       obs.stride(1), obs.stride(2), obs.stride(3), mode_code(mode),
+                       kind == "singleview" ? EKS_FIT_SINGLEVIEW : EKS_FIT_MULTICAM, smooth_param,
+                       quantile_keep, params.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel(),
+                       status.data_ptr<int32_t>(), yev.data_ptr(), ncomplete.data_ptr<int32_t>(),
+                       nkept.data_ptr<int32_t>(), cur_stream(obs)),
+          "eks_fit_gaps");
+  return {params, status, yev, ncomplete, nkept};
+}
+FitGaps fit_gaps_meta(const Tensor& obs, const std::string&, int64_t n, int64_t r, double, double,
+                      const std::string& mode) {
+  const auto i32o = obs.options().dtype(at::kInt);
+  const int64_t B = obs.size(0);
+  const size_t yb = eks_yev_bytes(B, obs.size(1), (int)n, obs_dtype(obs), (int)obs.size(2),
+                                  mode_code(mode));
+  return {at::empty({B, eks_param_len((int)n, (int)r)}, obs.options().dtype(at::kDouble)),
+          at::empty({B}, i32o), at::empty({(int64_t)yb}, obs.options().dtype(at::kByte)),
+          at::empty({B}, i32o), at::empty({B}, i32o)};
+}
+
 // ---------------------------------------------------------- newton_filter
 std::tuple<Tensor, Tensor> newton_gpu(const Tensor& y, const Tensor& ev, const Tensor& mu0,
                                       const Tensor& S0, const Tensor& A, const Tensor& Bm,
@@ -504,6 +545,8 @@ TORCH_LIBRARY(eks, m) {
         "(Tensor, Tensor, Tensor)");
   m.def("fit(Tensor obs, str kind, int n, int r, float smooth_param, float quantile_keep, "
         "str mode) -> (Tensor, Tensor)");
+  m.def("fit_gaps(Tensor obs, str kind, int n, int r, float smooth_param, float quantile_keep, "
+        "str mode) -> (Tensor params, Tensor status, Tensor yev, Tensor ncomplete, Tensor nkept)");
   m.def("newton_filter(Tensor y, Tensor ev, Tensor mu0, Tensor S0, Tensor A, Tensor Bm, "
         "Tensor E, int max_iter) -> (Tensor, Tensor)");
   m.def("interp1d(Tensor x, Tensor y, Tensor xq) -> Tensor");
@@ -520,6 +563,7 @@ TORCH_LIBRARY_IMPL(eks, CUDA, m) {
   m.impl("nll_sweep", &nll_sweep_gpu);
   m.impl("nll_sweep_gaps", &nll_sweep_gaps_gpu);
   m.impl("fit", &fit_gpu);
+  m.impl("fit_gaps", &fit_gaps_gpu);
   m.impl("newton_filter", &newton_gpu);
   m.impl("interp1d", &interp_gpu);
 }
@@ -535,6 +579,7 @@ TORCH_LIBRARY_IMPL(eks, Meta, m) {
   m.impl("nll_sweep", &nll_sweep_meta);
   m.impl("nll_sweep_gaps", &nll_sweep_gaps_meta);
   m.impl("fit", &fit_meta);
+  m.impl("fit_gaps", &fit_gaps_meta);
   m.impl("newton_filter", &newton_meta);
   m.impl("interp1d", &interp_meta);
 }

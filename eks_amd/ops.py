@@ -40,7 +40,7 @@ from . import _lib
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libeks_torch.so")
 
 OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "smooth_gaps", "nll",
-       "nll_sweep", "nll_sweep_gaps", "fit", "newton_filter", "interp1d")
+       "nll_sweep", "nll_sweep_gaps", "fit", "fit_gaps", "newton_filter", "interp1d")
 
 
 def _load():

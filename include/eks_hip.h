@@ -495,6 +495,35 @@ int eks_yev_dtype(int obs_dtype, int E, int mode);
 size_t eks_yev_bytes(int64_t B, int64_t T, int n, int obs_dtype, int E, int mode);
 
 /*
+ * eks_fit_gaps -- eks_fit through missing observations, with the missing
+ * rule of eks_smooth_gaps taken per frame: frame t of a trajectory is
+ * complete iff the ensemble average and the ensemble variance of all n
+ * columns are finite (no NaN or +-inf member, no overflowing variance).
+ * With M complete frames, the threshold is np.percentile(worst[complete],
+ * quantile_keep) with worst_t = max_j ev[t, j] (numpy's linear rule on the M
+ * values), a frame is kept iff it is complete and worst_t <= threshold, and
+ * everything else is eks_fit's over the kept frames in frame order -- the
+ * differences are those of consecutive KEPT frames whatever their distance
+ * in time.  That is the host fit on preds[ok], ev[ok] with ok the complete
+ * frames.  M = 0: status EKS_STATUS_SINGULAR, nkept 0; M = 1 or
+ * quantile_keep = 0: one kept frame (offset its average, S0 = 0, Q NaN,
+ * status 0).  On members without gaps params, status and the planes are
+ * bit-identical to eks_fit's.
+ * Arguments, limits and error codes as eks_fit, except that status (B) and
+ * yev (eks_yev_bytes) are required: the hand-off planes are written for
+ * every frame, non-finite where the frame is not complete, and are what
+ * eks_smooth_gaps / eks_nll_sweep_gaps read (eks_yev_dtype).  ncomplete,
+ * nkept (B) int32 or NULL: M and the number of kept frames.
+ * workspace: eks_fit_gaps_workspace_bytes (0 for unsupported shapes).
+ */
+size_t eks_fit_gaps_workspace_bytes(int64_t B, int64_t T, int n);
+int eks_fit_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
+                 int64_t sb, int64_t st, int64_t se, int64_t sj, int mode, int kind,
+                 double smooth_param, double quantile_keep, double *params,
+                 void *workspace, size_t workspace_bytes, int32_t *status, void *yev,
+                 int32_t *ncomplete, int32_t *nkept, void *stream);
+
+/*
  * eks_interp1d -- linear resampling for the asynchronous two-camera paw
  * smoother (F4), replacing the scipy.interpolate.interp1d(kind='linear')
  * calls of eks/multiview_pca_smoother.py:86-96 (which delegate to np.interp

@@ -35,7 +35,8 @@ def with_gaps(torch, obs, frac=0.1, hole=100, seed=1):
     frames of every trajectory."""
     B, T, E, n = obs.shape
     g = torch.Generator(device="cuda").manual_seed(seed)
-    tm = obs.permute(1, 2, 3, 0).contiguous()  # (T, E, n, B)
+    # (T, E, n, B); clone: .contiguous() of a time-major view is the view itself
+    tm = obs.permute(1, 2, 3, 0).clone(memory_format=torch.contiguous_format)
     miss = torch.rand((T, n, B), generator=g, device="cuda") < frac
     start = torch.randint(0, max(T - hole, 1), (B,), generator=g, device="cuda")
     t = torch.arange(T, device="cuda").unsqueeze(1)
