@@ -367,14 +367,30 @@ def fit_gaps(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_ke
     ncomplete (B,) int32 complete frames, nkept (B,) int32 kept frames).
     With ``check=True`` the call synchronises and raises ValueError when a
     trajectory has no complete frame (EKS_STATUS_SINGULAR in ``status``);
-    ``check=False`` leaves ``status`` to the caller."""
+    ``check=False`` leaves ``status`` to the caller.
+
+    ``obs`` may also be a ``Yev`` (from ``ensemble_gaps``, ``fit_gaps`` or
+    ``fit``): the fit then reads its planes instead of members, ``mode`` is
+    ignored, nothing is written to the planes and the returned ``yev`` is the
+    one passed in (``keep_yev`` must be left unset)."""
     torch = _lib.require_gpu()
-    if obs.dim() != 4 or obs.shape[3] != n:
-        raise ValueError("obs must be viewed as (B, T, E, n)")
-    B, T, E, _ = obs.shape
-    if obs.dtype not in (torch.float32, torch.float64):
-        raise TypeError("obs must be float32 or float64")
-    dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
+    from_yev = isinstance(obs, Yev)
+    if from_yev:
+        if keep_yev is not None:
+            raise ValueError("keep_yev cannot be combined with a Yev input: the planes are read, "
+                             "not written")
+        if obs.n != n:
+            raise ValueError(f"obs has {obs.n} coordinates, expected n={n}")
+        B, T, E = obs.B, obs.T, obs.E
+        dt = obs.code
+        mode = obs.mode
+    else:
+        if obs.dim() != 4 or obs.shape[3] != n:
+            raise ValueError("obs must be viewed as (B, T, E, n)")
+        B, T, E, _ = obs.shape
+        if obs.dtype not in (torch.float32, torch.float64):
+            raise TypeError("obs must be float32 or float64")
+        dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
     if mode not in ("median", "mean"):
         raise ValueError(f"{mode} averaging not supported")
     k = {"singleview": _lib.EKS_FIT_SINGLEVIEW, "multicam": _lib.EKS_FIT_MULTICAM}[kind]
@@ -392,8 +408,15 @@ def fit_gaps(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_ke
     ncomplete = torch.empty((B,), dtype=torch.int32, device=dev)
     nkept = torch.empty((B,), dtype=torch.int32, device=dev)
     ws = workspace(lib.eks_fit_gaps_workspace_bytes(B, T, n), dev, slot="fit_gaps")
-    sb, st, se, sj = obs.stride()
     m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
+    if from_yev:
+        _lib.check(lib.eks_fit_gaps(obs.buf.data_ptr(), dt, B, T, E, n, r, 0, 0, 0, 0, m, k,
+                                    float(smooth_param), float(quantile_keep), params.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), status.data_ptr(), None,
+                                    ncomplete.data_ptr(), nkept.data_ptr(), _lib.stream_ptr()),
+                   "eks_fit_gaps")
+        return _fit_gaps_result(check, B, params, status, obs, ncomplete, nkept)
+    sb, st, se, sj = obs.stride()
     nbytes = lib.eks_yev_bytes(B, T, n, dt, E, m)
     code = lib.eks_yev_dtype(dt, E, m)
     if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
@@ -408,6 +431,10 @@ def fit_gaps(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_ke
                                 ws.data_ptr(), ws.numel(), status.data_ptr(), yev.buf.data_ptr(),
                                 ncomplete.data_ptr(), nkept.data_ptr(), _lib.stream_ptr()),
                "eks_fit_gaps")
+    return _fit_gaps_result(check, B, params, status, yev, ncomplete, nkept)
+
+
+def _fit_gaps_result(check, B, params, status, yev, ncomplete, nkept):
     if check and B > 0:
         bad = int((ncomplete == 0).sum().item())
         if bad:
@@ -415,6 +442,51 @@ def fit_gaps(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_ke
         if bool((status != 0).any()):
             raise ValueError("eks_fit_gaps: no frame was kept")
     return dict(params=params, status=status, yev=yev, ncomplete=ncomplete, nkept=nkept)
+
+
+def ensemble_gaps(obs, *, n: int, mode: str = "median", min_members: int,
+                  want_nvalid: bool = False, keep_yev=None):
+    """The ensemble over the valid (finite) members of every column
+    (eks_ensemble_gaps): (B, T, E, n) member view, float32 or float64, any
+    strides -> dict(yev, nvalid).  A column is missing (NaN planes) only when
+    fewer than ``min_members`` of its E members are finite; otherwise y is the
+    nanmedian / nanmean and ev the nanvar / m of the m valid ones.
+
+    ``yev`` is a ``Yev`` (code EKS_YEV64) that ``smooth_gaps``,
+    ``nll_sweep_gaps`` and ``fit_gaps`` read in place of the members (the
+    buffer of ``keep_yev`` is reused when it is large enough); ``nvalid`` the
+    uint8 (T, n, B) counts m with ``want_nvalid``, else None.  A single valid
+    member has ev = 0, an exact observation to ``smooth_gaps``
+    (EKS_STATUS_SCAN): use ``min_members >= 2``."""
+    torch = _lib.require_gpu()
+    if obs.dim() != 4 or obs.shape[3] != n:
+        raise ValueError("obs must be viewed as (B, T, E, n)")
+    B, T, E, _ = obs.shape
+    if obs.dtype not in (torch.float32, torch.float64):
+        raise TypeError("obs must be float32 or float64")
+    dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    min_members = int(min_members)
+    if not 1 <= min_members <= E:
+        raise ValueError(f"min_members={min_members} outside 1..E={E}")
+    lib = _lib.load()
+    dev = obs.device
+    m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
+    nbytes = lib.eks_yev_bytes(B, T, n, _lib.EKS_F64, E, m)
+    if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
+        yev = Yev(keep_yev.buf, B, T, E, n, _lib.EKS_YEV64, mode)
+    else:
+        yev = Yev(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), B, T, E, n,
+                  _lib.EKS_YEV64, mode)
+    nvalid = torch.empty((T, n, B), dtype=torch.uint8, device=dev) if want_nvalid else None
+    sb, st, se, sj = obs.stride()
+    _lib.check(lib.eks_ensemble_gaps(obs.data_ptr(), dt, B, T, E, n, sb, st, se, sj, m,
+                                     min_members, yev.buf.data_ptr(),
+                                     nvalid.data_ptr() if nvalid is not None and B > 0 else None,
+                                     _lib.stream_ptr()),
+               "eks_ensemble_gaps")
+    return dict(yev=yev, nvalid=nvalid)
 
 
 def nll(obs, params, *, n: int, r: int, mode: str = "median", flags: int = 0, algo: int = 0,

@@ -60,8 +60,13 @@ def ensemble_array(stack, mode: str = "median"):
     return preds.cpu().numpy(), var.cpu().numpy()
 
 
-def ensemble_handoff(stack, mode: str = "median"):
+def ensemble_handoff(stack, mode: str = "median", min_members=None):
     """(E, T, n) member array -> (yev, preds (T, n), vars (T, n)).
+
+    ``min_members`` (an integer in 1..E) takes the ensemble over the valid
+    (finite) members of each column (eks_ensemble_gaps): a column is NaN only
+    when fewer than ``min_members`` are finite.  ``None`` is the all-members
+    ensemble, where one NaN member makes its column NaN.
 
     Like ``ensemble_array``, but the device ensemble is written straight into
     the y / ev hand-off planes that ``batch.smooth`` accepts in place of the
@@ -89,9 +94,17 @@ def ensemble_handoff(stack, mode: str = "median"):
     buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     if nbytes < ev_off + T * n * 8:
         raise RuntimeError("eks_yev_bytes smaller than the (T, n) y / ev planes")
-    _lib.check(lib.eks_ensemble(d.data_ptr(), _lib.EKS_F64, 1, T, E, n, 0, n, T * n, 1, m,
-                                buf.data_ptr(), buf.data_ptr() + ev_off, _lib.stream_ptr()),
-               "eks_ensemble")
+    if min_members is None:
+        _lib.check(lib.eks_ensemble(d.data_ptr(), _lib.EKS_F64, 1, T, E, n, 0, n, T * n, 1, m,
+                                    buf.data_ptr(), buf.data_ptr() + ev_off, _lib.stream_ptr()),
+                   "eks_ensemble")
+    else:
+        if int(min_members) != min_members or not 1 <= min_members <= E:
+            raise ValueError(f"min_members={min_members!r} must be an integer in 1..E={E}")
+        _lib.check(lib.eks_ensemble_gaps(d.data_ptr(), _lib.EKS_F64, 1, T, E, n, 0, n, T * n, 1,
+                                         m, int(min_members), buf.data_ptr(), None,
+                                         _lib.stream_ptr()),
+                   "eks_ensemble_gaps")
     planes = buf[:ev_off + T * n * 8]
     preds = planes[:T * n * 8].view(torch.float64).reshape(T, n).cpu().numpy()
     var = planes[ev_off:].view(torch.float64).reshape(T, n).cpu().numpy()

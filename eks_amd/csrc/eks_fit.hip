@@ -17,6 +17,8 @@
 //   k_fit_worst   one lane per (trajectory, chunk of frames): ensemble of
 //                 every frame (same code as eks_ensemble), v_t = max_j var
 //                 stored trajectory-major
+//   k_fit_worst_yev  the same from y / ev hand-off planes (eks_fit_gaps with
+//                 EKS_YEV32 / EKS_YEV64 input: the fit from planes)
 //   k_fit_select  one 256-thread block per trajectory: exact order
 //                 statistics v_(lo), v_(lo+1) by MSD radix select on the
 //                 IEEE bit patterns (12-bit digits, LDS histograms, early
@@ -243,6 +245,87 @@ __global__ __launch_bounds__(256) void k_fit_worst(const T *__restrict__ obs, Fi
           frame_ensemble<E, N, T>(pb + u * st, se, sj, Ert, median != 0, y, ev, v);
           worst[b * sh.T + u] = v;
           frame_out(u, y, ev);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 256 / 16; ++p) {
+      const int r = p * 16 + (threadIdx.x >> 4), k = threadIdx.x & 15;
+      const long long o = base[r];
+      if (o >= 0) worst[o + k] = tile[r][k];
+    }
+    __syncthreads();
+  }
+}
+
+// The worst pass of the fit from planes (eks_fit_gaps with EKS_YEV32 /
+// EKS_YEV64 input): worst[b*T + t] = max_j ev[t, j], NaN when any y or ev of
+// the frame is not finite (frame_ensemble's rule on what the planes hold), and
+// the shift K = frame 0's y.  k_fit_worst's lanes and tiles with a runtime n:
+// per column the 16 frames of the tile are loaded together (32 plane loads in
+// flight per lane, each one row segment per wave).
+template <typename YT>
+__global__ __launch_bounds__(256) void k_fit_worst_yev(YevOut yi, FitShape sh, int n,
+                                                       double *__restrict__ worst, FitShift ks) {
+  __shared__ double tile[256][kTile + 1];
+  __shared__ long long base[256];
+  constexpr unsigned long long kExpAll = 0x7ff0000000000000ull;
+  const long long lane = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  const bool active = lane < sh.B * sh.NC;
+  long long b = 0, t0 = 0, t1 = 0;
+  if (active) {
+    b = lane % sh.B;
+    t0 = (lane / sh.B) * sh.Lc;
+    t1 = t0 + sh.Lc < sh.T ? t0 + sh.Lc : sh.T;
+  }
+  const YT *yp = (const YT *)yi.y;
+  const double *ep = yi.ev;
+  auto finite = [&](double x) {
+    return ((unsigned long long)__double_as_longlong(x) & kExpAll) != kExpAll;
+  };
+  const long long ntiles = sh.Lc / kTile;  // Lc is a multiple of kTile
+  for (long long kt = 0; kt < ntiles; ++kt) {
+    const long long t = t0 + kt * kTile;
+    if (active && t + kTile <= t1) {
+      double v[kTile];
+      bool bad[kTile];
+#pragma unroll
+      for (int k = 0; k < kTile; ++k) {
+        v[k] = -1.0;
+        bad[k] = false;
+      }
+      for (int j = 0; j < n; ++j) {
+        double yv[kTile], e[kTile];
+#pragma unroll
+        for (int k = 0; k < kTile; ++k) {
+          const long long o = ((t + k) * n + j) * sh.B + b;
+          yv[k] = (double)yp[o];
+          e[k] = ep[o];
+        }
+        if (t == 0) ks.K[b * n + j] = yv[0];
+#pragma unroll
+        for (int k = 0; k < kTile; ++k) {
+          bad[k] |= !finite(yv[k]) || !finite(e[k]);
+          v[k] = e[k] > v[k] ? e[k] : v[k];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kTile; ++k) tile[threadIdx.x][k] = bad[k] ? __builtin_nan("") : v[k];
+      base[threadIdx.x] = b * sh.T + t;
+    } else {
+      base[threadIdx.x] = -1;
+      if (active)
+        for (long long u = t; u < t1; ++u) {  // ragged end of the last chunk
+          double v = -1.0;
+          bool bad = false;
+          for (int j = 0; j < n; ++j) {
+            const long long o = (u * n + j) * sh.B + b;
+            const double yv = (double)yp[o], e = ep[o];
+            if (u == 0) ks.K[b * n + j] = yv;
+            bad |= !finite(yv) || !finite(e);
+            v = e > v ? e : v;
+          }
+          worst[b * sh.T + u] = bad ? __builtin_nan("") : v;
         }
     }
     __syncthreads();
@@ -2153,14 +2236,25 @@ static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, in
                    void *workspace, size_t workspace_bytes, int32_t *status, void *yev,
                    int32_t *ncomplete, int32_t *nkept, void *stream) {
   clear_err();
-  if (!obs || !params || !workspace || (gaps && (!status || !yev)))
+  // the fit from planes (eks_fit_gaps only): obs is a y / ev hand-off buffer,
+  // read where the member path reads the planes it wrote itself
+  const bool planes = gaps && (obs_dtype == EKS_YEV32 || obs_dtype == EKS_YEV64);
+  if (!obs || !params || !workspace || (gaps && (!status || (!yev && !planes))))
     return set_err(EKS_ERR_ARG, "%s: NULL pointer", fn);
+  if (planes) {
+    if (yev && yev != obs)
+      return set_err(EKS_ERR_ARG, "%s: with hand-off planes as input yev must be NULL or obs", fn);
+    yev = const_cast<void *>(obs);
+    E = 1;  // (ignored, as the strides and mode)
+    mode = EKS_MEDIAN;
+  }
   if (B < 0 || T < 2 || E < 1 || n < 1) return set_err(EKS_ERR_ARG, "%s: bad sizes", fn);
   if (B == 0) return EKS_OK;
   if (E > kMaxMembers) return set_err(EKS_ERR_UNSUPPORTED, "%s: E=%d > %d", fn, E, kMaxMembers);
   if (mode != EKS_MEDIAN && mode != EKS_MEAN)
     return set_err(EKS_ERR_ARG, "%d averaging not supported", mode);
-  if (obs_dtype != EKS_F32 && obs_dtype != EKS_F64) return set_err(EKS_ERR_ARG, "bad dtype");
+  if (!planes && obs_dtype != EKS_F32 && obs_dtype != EKS_F64)
+    return set_err(EKS_ERR_ARG, "bad dtype");
   if (kind != EKS_FIT_SINGLEVIEW && kind != EKS_FIT_MULTICAM)
     return set_err(EKS_ERR_ARG, "%s: unknown model kind %d", fn, kind);
   if (kind == EKS_FIT_SINGLEVIEW && r != n)
@@ -2206,7 +2300,7 @@ static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, in
   const double g = vi - (double)lo;
   const int median = mode == EKS_MEDIAN ? 1 : 0;
   const unsigned grid = grid_for(B * sh.NC, 256);
-  const bool y32 = yev_float(obs_dtype, E, mode);
+  const bool y32 = planes ? obs_dtype == EKS_YEV32 : yev_float(obs_dtype, E, mode);
   YevOut yo;
   if (yev) {
     yo.y = yev;
@@ -2288,30 +2382,40 @@ static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, in
   if (n > kMaxObs) {  // 5-8 cameras: the wide kernels (runtime n, runtime E)
     if (kind != EKS_FIT_MULTICAM || r != 3)
       return set_err(EKS_ERR_UNSUPPORTED, "%s: n=%d needs the PCA model with r = 3", fn, n);
-    auto wide_e = [&](auto tag, auto ytag, auto Ec) -> int {
+    auto wide_e = [&](auto tag, auto ytag, auto Ec, auto Pl) -> int {
       using Tp = decltype(tag);
       using YT = decltype(ytag);
       constexpr int EE = decltype(Ec)::value;
+      constexpr bool kPlanes = decltype(Pl)::value != 0;  // the fit from planes
       prof_call_begin();
-      prof_mark(s, "k_fitw_worst");
       int ncw;
       long long lcw;
       fit_chunks(B, T, ncw, lcw);  // k_fit_worst's lanes (one per (trajectory, chunk))
       const FitShape shw{B, T, ncw, lcw};
-      hipLaunchKernelGGL((k_fitw_worst<Tp, YT, EE>), dim3(grid_for(B * (long long)ncw, 256)), dim3(256), 0, s,
-                         (const Tp *)obs, shw, sb, st, se, sj, E, n, median, worst, yo, ks, zs);
-      int rc = check_launch("k_fitw_worst");
+      int rc;
+      if constexpr (kPlanes) {
+        prof_mark(s, "k_fit_worst_yev");
+        hipLaunchKernelGGL((k_fit_worst_yev<YT>), dim3(grid_for(B * (long long)ncw, 256)),
+                           dim3(256), 0, s, yo, shw, n, worst, ks);
+        rc = check_launch("k_fit_worst_yev");
+      } else {
+        prof_mark(s, "k_fitw_worst");
+        hipLaunchKernelGGL((k_fitw_worst<Tp, YT, EE>), dim3(grid_for(B * (long long)ncw, 256)), dim3(256), 0, s,
+                           (const Tp *)obs, shw, sb, st, se, sj, E, n, median, worst, yo, ks, zs);
+        rc = check_launch("k_fitw_worst");
+      }
       if (rc || (rc = select())) return rc;
       prof_mark(s, "k_fitw_accum");
       const unsigned ga = grid_for(B * (long long)sh.NC * kNW, 256);
-      if (yev)
+      if (kPlanes || yev) {
         hipLaunchKernelGGL((k_fitw_accum<Tp, YT, true, 0>), dim3(ga), dim3(256), 0, s,
                            (const Tp *)obs, sh, sb, st, se, sj, E, n, median, thr, kept, W, partA,
                            yo, ks);
-      else
+      } else if constexpr (!kPlanes) {
         hipLaunchKernelGGL((k_fitw_accum<Tp, YT, false, EE>), dim3(ga), dim3(256), 0, s,
                            (const Tp *)obs, sh, sb, st, se, sj, E, n, median, thr, kept, W, partA,
                            yo, ks);
+      }
       if ((rc = check_launch("k_fitw_accum"))) return rc;
       double *src = merge(ic<0>{}, npart);
       if (!src) return EKS_ERR_HIP;
@@ -2323,12 +2427,17 @@ static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, in
     };
     auto wide = [&](auto tag, auto ytag) -> int {
       switch (E) {
-        case 3: return wide_e(tag, ytag, ic<3>{});
-        case 4: return wide_e(tag, ytag, ic<4>{});
-        case 5: return wide_e(tag, ytag, ic<5>{});
-        default: return wide_e(tag, ytag, ic<0>{});
+        case 3: return wide_e(tag, ytag, ic<3>{}, ic<0>{});
+        case 4: return wide_e(tag, ytag, ic<4>{}, ic<0>{});
+        case 5: return wide_e(tag, ytag, ic<5>{}, ic<0>{});
+        default: return wide_e(tag, ytag, ic<0>{}, ic<0>{});
       }
     };
+    // (the plane path's accumulation ignores the member type: the tags of
+    // instantiations the member path has anyway)
+    if (planes)
+      return y32 ? wide_e(float{}, float{}, ic<0>{}, ic<1>{})
+                 : wide_e(double{}, double{}, ic<0>{}, ic<1>{});
     if (y32) return wide(float{}, float{});
     return obs_dtype == EKS_F32 ? wide(float{}, double{}) : wide(double{}, double{});
   }
@@ -2345,13 +2454,22 @@ static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, in
     auto by_type = [&](auto tag, auto ytag) -> int {
       using Tp = decltype(tag);
       using YT = decltype(ytag);
-      auto by_e = [&](auto Ec) -> int {
+      auto by_e = [&](auto Ec, auto Pl) -> int {
         constexpr int EE = decltype(Ec)::value;
+        constexpr bool kPlanes = decltype(Pl)::value != 0;  // the fit from planes
         prof_call_begin();
-        prof_mark(s, "k_fit_worst");
-        hipLaunchKernelGGL((k_fit_worst<EE, NN, Tp, YT>), dim3(grid), dim3(256), 0, s,
-                           (const Tp *)obs, sh, sb, st, se, sj, E, median, worst, yo, ks, zs);
-        int rc = check_launch("k_fit_worst");
+        int rc;
+        if constexpr (kPlanes) {
+          prof_mark(s, "k_fit_worst_yev");
+          hipLaunchKernelGGL((k_fit_worst_yev<YT>), dim3(grid), dim3(256), 0, s, yo, sh, n, worst,
+                             ks);
+          rc = check_launch("k_fit_worst_yev");
+        } else {
+          prof_mark(s, "k_fit_worst");
+          hipLaunchKernelGGL((k_fit_worst<EE, NN, Tp, YT>), dim3(grid), dim3(256), 0, s,
+                             (const Tp *)obs, sh, sb, st, se, sj, E, median, worst, yo, ks, zs);
+          rc = check_launch("k_fit_worst");
+        }
         if (rc) return rc;
         if ((rc = select())) return rc;
         prof_mark(s, "k_fit_accum");
@@ -2369,10 +2487,10 @@ static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, in
                              dim3(256), 0, s, (const TA *)obs, sh, sb, st, se, sj, E, median, thr,
                              kept, W, partA, yo, ks);
         };
-        if (yev) {
+        if (kPlanes || yev) {
           if (wave_merge) accum(ic<1>{}, ic<1>{});
           else accum(ic<1>{}, ic<0>{});
-        } else {
+        } else if constexpr (!kPlanes) {
           if (wave_merge) accum(ic<0>{}, ic<1>{});
           else accum(ic<0>{}, ic<0>{});
         }
@@ -2393,13 +2511,15 @@ static int fit_run(const char *fn, bool gaps, const void *obs, int obs_dtype, in
         prof_call_end(s);
         return rc;
       };
+      if (planes) return by_e(ic<0>{}, ic<1>{});
       switch (E) {
-        case 3: return by_e(ic<3>{});
-        case 4: return by_e(ic<4>{});
-        case 5: return by_e(ic<5>{});
-        default: return by_e(ic<0>{});
+        case 3: return by_e(ic<3>{}, ic<0>{});
+        case 4: return by_e(ic<4>{}, ic<0>{});
+        case 5: return by_e(ic<5>{}, ic<0>{});
+        default: return by_e(ic<0>{}, ic<0>{});
       }
     };
+    if (planes) return y32 ? by_type(float{}, float{}) : by_type(double{}, double{});
     if (y32) return by_type(float{}, float{});
     return obs_dtype == EKS_F32 ? by_type(float{}, double{}) : by_type(double{}, double{});
   });

@@ -208,6 +208,162 @@ EKS_DEV void ensemble_reduce_rt(const T *p, long long se, int E, bool median, do
   }
 }
 
+// ---------------------------------------------------------------------------
+// The ensemble over the VALID members of a column (eks_ensemble_gaps): member
+// e is valid iff it is finite (NaN, +inf and -inf are skipped), m counts the
+// valid ones, and with m >= max(min_members, 1)
+//   mean = sum(z) * (1/m)                 z_e = the member, +0 where skipped
+//   var  = sum(d) * (1/m^2)               d_e = (z_e - mean)^2, 0 where skipped
+//   median: middle order statistic of the valid members, or (lo + hi) / 2
+// (np.nanmean, np.nanvar(ddof=0) / m, np.nanmedian; the sums keep np_sum's
+// order over all E slots, so a column whose members are all valid has the
+// bits of ensemble_reduce).  Fewer valid members: avg = var = NaN.
+// ---------------------------------------------------------------------------
+template <typename T>
+EKS_DEV bool member_valid(T v) {
+  return __builtin_fabs(to_f64(v)) < __builtin_inf();  // false for NaN
+}
+
+// 1 / m and 1 / m^2 for m in 1..E as compile-time constants (the doubles
+// ensemble_reduce uses at m = E), picked by an unrolled select
+template <int E>
+EKS_DEV void valid_recips(int m, double &inv, double &inv2) {
+  inv = 1.0;
+  inv2 = 1.0;
+#pragma unroll
+  for (int k = 2; k <= E; ++k) {
+    inv = m == k ? 1.0 / (double)k : inv;
+    inv2 = m == k ? 1.0 / ((double)k * (double)k) : inv2;
+  }
+}
+
+template <int E, typename T>
+EKS_DEV void ensemble_reduce_valid(const T (&raw)[E], bool median, int min_members, double &avg,
+                                   double &var, int &m) {
+  bool ok[E];
+  m = 0;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    ok[e] = member_valid(raw[e]);
+    m += ok[e] ? 1 : 0;
+  }
+  // wave-uniform fast path: every column of the wave complete -> the very
+  // code (and bits) of ensemble_reduce
+  if (__builtin_amdgcn_ballot_w64(m != E) == 0) {
+    ensemble_reduce<E, T>(raw, median, avg, var);
+    return;
+  }
+  asm volatile("");  // not speculated into the fast path
+  double inv, inv2;
+  valid_recips<E>(m, inv, inv2);
+  double x[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) x[e] = ok[e] ? to_f64(raw[e]) : 0.0;
+  const double mean = rounded(np_sum<E>(x) * inv);
+  // (the select sits on the difference, so the squares and their sums keep
+  // ensemble_reduce's expression and contraction)
+  double d[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const double t = ok[e] ? x[e] - mean : 0.0;
+    d[e] = t * t;
+  }
+  var = rounded(np_sum<E>(d) * inv2);
+  if (median) {
+    const T pinf = static_cast<T>(__builtin_inf());
+    T v[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) v[e] = ok[e] ? raw[e] : pinf;  // skipped members sort last
+    sort_net<E, T>(v);
+    // order statistics (m - 1) / 2 and m / 2 by an unrolled select (a runtime
+    // index would send v to scratch)
+    const int klo = (m - 1) >> 1, khi = m >> 1;
+    T lo = v[0], hi = v[0];
+#pragma unroll
+    for (int e = 1; e < E; ++e) {
+      lo = klo == e ? v[e] : lo;
+      hi = khi == e ? v[e] : hi;
+    }
+    avg = (m & 1) ? to_f64(hi) : (to_f64(lo) + to_f64(hi)) / 2.0;
+  } else {
+    avg = mean;
+  }
+  if (m < (min_members > 1 ? min_members : 1)) {
+    avg = __builtin_nan("");
+    var = __builtin_nan("");
+  }
+}
+
+// numpy pairwise_sum order over f(0..E-1), runtime E (ensemble_reduce_rt's)
+template <typename F>
+EKS_DEV double np_sum_rt(int E, F &&f) {
+  if (E < 8) {
+    double s = f(0);
+    for (int i = 1; i < E; ++i) s += f(i);
+    return s;
+  }
+  double r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = f(j);
+  const int full = E - (E % 8);
+  for (int i = 8; i < full; i += 8)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] += f(i + j);
+  double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (int k = full; k < E; ++k) s += f(k);
+  return s;
+}
+
+// The runtime-E twin, reading members straight from memory (O(E^2) rank
+// selection among the valid members).
+template <typename T>
+EKS_DEV void ensemble_reduce_valid_rt(const T *p, long long se, int E, bool median,
+                                      int min_members, double &avg, double &var, int &m) {
+  m = 0;
+  for (int e = 0; e < E; ++e) m += member_valid(p[(long long)e * se]) ? 1 : 0;
+  if (__builtin_amdgcn_ballot_w64(m != E) == 0) {
+    ensemble_reduce_rt<T>(p, se, E, median, avg, var);
+    return;
+  }
+  asm volatile("");
+  if (m < (min_members > 1 ? min_members : 1)) {
+    avg = __builtin_nan("");
+    var = __builtin_nan("");
+    return;
+  }
+  const double dm = (double)m;
+  const double inv = 1.0 / dm, inv2 = 1.0 / (dm * dm);
+  const double mean = rounded(np_sum_rt(E, [&](int i) {
+                                const T v = p[(long long)i * se];
+                                return member_valid(v) ? to_f64(v) : 0.0;
+                              }) * inv);
+  var = rounded(np_sum_rt(E, [&](int i) {
+          const T v = p[(long long)i * se];
+          const double t = member_valid(v) ? to_f64(v) - mean : 0.0;
+          return t * t;
+        }) * inv2);
+  if (median) {
+    const int k_lo = (m - 1) >> 1, k_hi = m >> 1;
+    double v_lo = 0.0, v_hi = 0.0;
+    for (int i = 0; i < E; ++i) {
+      const T xi = p[(long long)i * se];
+      if (!member_valid(xi)) continue;
+      int less = 0, eq = 0;
+      for (int j = 0; j < E; ++j) {
+        const T xj = p[(long long)j * se];  // (a NaN compares false; +-inf are masked)
+        const bool vj = member_valid(xj);
+        less += (vj && xj < xi);
+        eq += (vj && xj == xi);
+      }
+      if (less <= k_lo && k_lo < less + eq) v_lo = to_f64(xi);
+      if (less <= k_hi && k_hi < less + eq) v_hi = to_f64(xi);
+    }
+    avg = (m & 1) ? v_hi : (v_lo + v_hi) / 2.0;
+  } else {
+    avg = mean;
+  }
+}
+
 // One coordinate's ensemble from memory (members se apart): the compiled-E
 // reduction on registers when E > 0, else the runtime-E one.  The
 // runtime-n kernels use it so that the common member counts (3, 4, 5) do not

@@ -22,6 +22,7 @@
 //   eks::nll_sweep_gaps(obs, params, K, n, r, mode)  the same through missing observations
 //   eks::fit(obs, kind, n, r, s, q, mode)          eks/multiview_pca_smoother.py:684-731
 //   eks::fit_gaps(obs, kind, n, r, s, q, mode)     the same through missing observations
+//   eks::ensemble_gaps(obs, mode, min_members)     the ensemble over the valid members
 //   eks::newton_filter(y, ev, mu0, S0, A, Bm, E, max_iter)  eks/newton_eks.py:115-148
 //   eks::interp1d(x, y, xq)                        eks/multiview_pca_smoother.py:86-96
 #include <ATen/ATen.h>
@@ -470,6 +471,35 @@ FitGaps fit_gaps_meta(const Tensor& obs, const std::string&, int64_t n, int64_t 
           at::empty({B}, i32o), at::empty({B}, i32o)};
 }
 
+// ----------------------------------------------------------- ensemble_gaps
+// (yev bytes: EKS_YEV64 planes; nvalid (T, n, B) uint8, the valid members of
+// every column in the planes' layout)
+std::tuple<Tensor, Tensor> ensemble_gaps_gpu(const Tensor& obs, const std::string& mode,
+                                             int64_t min_members) {
+  need_gpu(obs, "obs");
+  TORCH_CHECK(obs.dim() == 4, "obs must be viewed as (B, T, E, n)");
+  const c10::DeviceGuard g(obs.device());
+  const int64_t B = obs.size(0), T = obs.size(1), E = obs.size(2), n = obs.size(3);
+  TORCH_CHECK(min_members >= 1 && min_members <= E, "min_members must be in 1..E=", E);
+  const size_t yb = eks_yev_bytes(B, T, (int)n, EKS_F64, (int)E, mode_code(mode));
+  Tensor yev = at::empty({(int64_t)yb}, obs.options().dtype(at::kByte));
+  Tensor nvalid = at::empty({T, n, B}, obs.options().dtype(at::kByte));
+  if (B > 0)  // (an empty batch has no planes to point at)
+    check(eks_ensemble_gaps(obs.data_ptr(), obs_dtype(obs), B, T, (int)E, (int)n, obs.stride(0),
+                            obs.stride(1), obs.stride(2), obs.stride(3), mode_code(mode),
+                            (int)min_members, yev.data_ptr(), nvalid.data_ptr<uint8_t>(),
+                            cur_stream(obs)),
+          "eks_ensemble_gaps");
+  return {yev, nvalid};
+}
+std::tuple<Tensor, Tensor> ensemble_gaps_meta(const Tensor& obs, const std::string& mode,
+                                              int64_t) {
+  const int64_t B = obs.size(0), T = obs.size(1), n = obs.size(3);
+  const size_t yb = eks_yev_bytes(B, T, (int)n, EKS_F64, (int)obs.size(2), mode_code(mode));
+  return {at::empty({(int64_t)yb}, obs.options().dtype(at::kByte)),
+          at::empty({T, n, B}, obs.options().dtype(at::kByte))};
+}
+
 // ---------------------------------------------------------- newton_filter
 std::tuple<Tensor, Tensor> newton_gpu(const Tensor& y, const Tensor& ev, const Tensor& mu0,
                                       const Tensor& S0, const Tensor& A, const Tensor& Bm,
@@ -547,6 +577,7 @@ TORCH_LIBRARY(eks, m) {
         "str mode) -> (Tensor, Tensor)");
   m.def("fit_gaps(Tensor obs, str kind, int n, int r, float smooth_param, float quantile_keep, "
         "str mode) -> (Tensor params, Tensor status, Tensor yev, Tensor ncomplete, Tensor nkept)");
+  m.def("ensemble_gaps(Tensor obs, str mode, int min_members) -> (Tensor, Tensor)");
   m.def("newton_filter(Tensor y, Tensor ev, Tensor mu0, Tensor S0, Tensor A, Tensor Bm, "
         "Tensor E, int max_iter) -> (Tensor, Tensor)");
   m.def("interp1d(Tensor x, Tensor y, Tensor xq) -> Tensor");
@@ -564,6 +595,7 @@ TORCH_LIBRARY_IMPL(eks, CUDA, m) {
   m.impl("nll_sweep_gaps", &nll_sweep_gaps_gpu);
   m.impl("fit", &fit_gpu);
   m.impl("fit_gaps", &fit_gaps_gpu);
+  m.impl("ensemble_gaps", &ensemble_gaps_gpu);
   m.impl("newton_filter", &newton_gpu);
   m.impl("interp1d", &interp_gpu);
 }
@@ -580,6 +612,7 @@ TORCH_LIBRARY_IMPL(eks, Meta, m) {
   m.impl("nll_sweep_gaps", &nll_sweep_gaps_meta);
   m.impl("fit", &fit_meta);
   m.impl("fit_gaps", &fit_gaps_meta);
+  m.impl("ensemble_gaps", &ensemble_gaps_meta);
   m.impl("newton_filter", &newton_meta);
   m.impl("interp1d", &interp_meta);
 }

@@ -28,6 +28,9 @@ CPU tensor is a dispatch error).  Layout conventions are those of
     smooth_gaps (obs, params, n, r, mode) -> (out, var (B,T,n), nll (B), nobs (B), status):
                the smoother through missing observations (non-finite ensemble average
                or variance), its posterior variances and the NLL over the observed entries
+    ensemble_gaps (obs, mode, min_members) -> (yev bytes (EKS_YEV64 planes), nvalid (T,n,B) uint8):
+               the ensemble over the finite members of each column, missing only where
+               fewer than min_members are finite
 """
 from __future__ import annotations
 
@@ -40,7 +43,7 @@ from . import _lib
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libeks_torch.so")
 
 OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "smooth_gaps", "nll",
-       "nll_sweep", "nll_sweep_gaps", "fit", "fit_gaps", "newton_filter", "interp1d")
+       "nll_sweep", "nll_sweep_gaps", "fit", "fit_gaps", "ensemble_gaps", "newton_filter", "interp1d")
 
 
 def _load():

@@ -84,9 +84,23 @@ def _auto_smooth_param(yev, model: dict, mode: str = "median") -> float:
     return float(sel["smooth_param"][0].item())
 
 
+def _check_min_members(min_members, allow_missing):
+    """``min_members`` (the ensemble over the valid members of each column,
+    core.ensemble_handoff) changes what is missing: only with allow_missing."""
+    if min_members is not None and not allow_missing:
+        raise ValueError("min_members needs allow_missing=True")
+
+
+# ``min_members`` (with ``allow_missing=True`` only), in every wrapper below:
+# the ensemble is taken over the finite members of each column
+# (batch.ensemble_gaps) and a column is missing only when fewer than
+# ``min_members`` of them are finite -- one rejected member no longer discards
+# its frame.  ``None``: a NaN prediction of any member makes its column missing.
+
+
 def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, smooth_param,
                                        quantile_keep_pca, camera_names, posterior_var=False,
-                                       allow_missing=False):
+                                       allow_missing=False, min_members=None):
     """Multi-view PCA smoother for one keypoint (eks/multiview_pca_smoother.py:611-767).
 
     ``smooth_param=None``: chosen by minimising the filter's NLL on the device
@@ -98,7 +112,9 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
     model is fitted on the frames that are complete in every column, the
     smoother steps over the gaps (batch.smooth_gaps) and every frame of the
     output is finite.  The dict gains 'n_missing', the number of missing
-    entries.  It needs a ``smooth_param``.
+    entries.  It needs a ``smooth_param``.  With ``min_members`` a column is
+    missing only when fewer than that many members are finite, and the
+    ensemble is taken over the finite ones (batch.ensemble_gaps).
 
     markers_list_cameras[camera][model] is a DataFrame whose first two
     columns are that camera's x and y predictions.  Returns
@@ -106,6 +122,7 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
     columns; likelihood is NaN as in the reference.  With ``posterior_var``
     the dict gains 'posterior_var_df': {f'{camera}_df': DataFrame} in the same
     layout, x / y holding the posterior variances of the smoothed x / y."""
+    _check_min_members(min_members, allow_missing)
     V = len(camera_names)
     if V < 2:
         raise ValueError("ensemble_kalman_smoother_multi_cam needs at least two cameras "
@@ -118,7 +135,7 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
     if allow_missing and smooth_param is None:
         raise ValueError("allow_missing=True needs a smooth_param: the likelihood sweep does "
                          "not step over gaps")
-    yev, preds, ev = core.ensemble_handoff(stack)
+    yev, preds, ev = core.ensemble_handoff(stack, min_members=min_members)
     auto = smooth_param is None
     dfs = {}
     if allow_missing:
@@ -160,7 +177,7 @@ def _run_gaps_pupil(yev, model: dict, pv: bool):
 
 def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
                                    state_transition_matrix, posterior_var=False,
-                                   allow_missing=False):
+                                   allow_missing=False, min_members=None):
     """IBL pupil smoother (eks/pupil_smoother.py:82-223).
 
     ``allow_missing=True``: a column whose ensemble average or variance is not
@@ -168,15 +185,17 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
     the model is fitted on the frames that are complete in every column, the
     smoother steps over the gaps (batch.smooth_gaps) and every frame of the
     output is finite.  The dict gains 'n_missing', the number of missing
-    entries.
+    entries.  With ``min_members`` a column is missing only when fewer than
+    that many members are finite (the ensemble over the finite ones).
 
     Returns {'markers_df': smoothed keypoints in the order top, right, bottom,
     left (NaN likelihood), 'latents_df': diameter, com_x, com_y}.  With
     ``posterior_var`` also 'posterior_var_df' (the markers layout, x / y holding
     the posterior variances) and 'latents_posterior_var_df' (diag(Vs))."""
+    _check_min_members(min_members, allow_missing)
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
-    yev, preds, ev = core.ensemble_handoff(stack)
+    yev, preds, ev = core.ensemble_handoff(stack, min_members=min_members)
     pv = bool(posterior_var)
     n_missing = None
     if allow_missing:
@@ -210,7 +229,7 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
 
 
 def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s_grid,
-                          com_s_grid, allow_missing=False):
+                          com_s_grid, allow_missing=False, min_members=None):
     """The pupil smoother with its smoothing parameters chosen by likelihood.
 
     Every (diameter_s, com_s) pair of the grid defines a model
@@ -224,13 +243,15 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
     ``allow_missing=True``: the candidates are fitted on the complete frames
     (they share C and offset and differ in A and Q), scored over the observed
     entries in one batch.nll_sweep_gaps call, and the argmin is smoothed
-    through the gaps (ensemble_kalman_smoother_pupil(allow_missing=True))."""
+    through the gaps (ensemble_kalman_smoother_pupil(allow_missing=True));
+    ``min_members`` as there."""
+    _check_min_members(min_members, allow_missing)
     torch = _lib.require_gpu()
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
     E, T, n = stack.shape
     if allow_missing:
-        yev, preds, ev = core.ensemble_handoff(stack)
+        yev, preds, ev = core.ensemble_handoff(stack, min_members=min_members)
         ok = _complete_frames(preds, ev)
         grid = [(d, c) for d in diameter_s_grid for c in com_s_grid]
         models = [fit.pupil_model(preds[ok], np.diag([d, c, c])) for d, c in grid]
@@ -242,7 +263,7 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
         best = grid[int(np.argmin(scores))]
         res = ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
                                              np.diag([best[0], best[1], best[1]]),
-                                             allow_missing=True)
+                                             allow_missing=True, min_members=min_members)
         res["nll"] = scores.reshape(len(diameter_s_grid), len(com_s_grid))
         res["best"] = best
         return res
@@ -266,7 +287,8 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
 
 def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth_param,
                                          quantile_keep_pca=25, ensembling_mode="median",
-                                         posterior_var=False, allow_missing=False):
+                                         posterior_var=False, allow_missing=False,
+                                         min_members=None):
     """Single-view EKS for one keypoint (the reference
     snapshot has no single-view smoother).
 
@@ -274,7 +296,9 @@ def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth
     not finite (a NaN prediction of any member) is a missing observation; the
     model is fitted on the complete frames, the smoother steps over the gaps
     (batch.smooth_gaps), 'nll' is the NLL over the observed entries and the
-    dict gains 'n_missing'.  It needs a ``smooth_param``.
+    dict gains 'n_missing'.  It needs a ``smooth_param``.  With
+    ``min_members`` a coordinate is missing only when fewer than that many
+    members are finite (the ensemble over the finite ones).
 
     markers_list: E DataFrames with '{keypoint}_x' / '{keypoint}_y' columns.
     Model: C = A = I2, m0 = 0, S0 = diag(var), Q = s cov(diff) over the
@@ -284,13 +308,14 @@ def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth
     ``smooth_param=None``: chosen by minimising the filter's NLL on the device
     (batch.select_smooth_param); the dict then gains 'smooth_param', and the
     frames equal those of a call with that value."""
+    _check_min_members(min_members, allow_missing)
     keys = [f"{keypoint_ensemble}_x", f"{keypoint_ensemble}_y"]
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in keys], 1)
                       for df in markers_list])  # (E, T, 2)
     if allow_missing and smooth_param is None:
         raise ValueError("allow_missing=True needs a smooth_param: the likelihood sweep does "
                          "not step over gaps")
-    yev, preds, ev = core.ensemble_handoff(stack, ensembling_mode)
+    yev, preds, ev = core.ensemble_handoff(stack, ensembling_mode, min_members=min_members)
     auto = smooth_param is None
     n_missing = None
     if allow_missing:

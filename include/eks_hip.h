@@ -522,6 +522,48 @@ int eks_fit_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, in
                  double smooth_param, double quantile_keep, double *params,
                  void *workspace, size_t workspace_bytes, int32_t *status, void *yev,
                  int32_t *ncomplete, int32_t *nkept, void *stream);
+/*
+ * The fit from planes: eks_fit_gaps also accepts obs_dtype = EKS_YEV32 /
+ * EKS_YEV64.  obs is then a y / ev hand-off buffer for (B, T, n) -- written
+ * by eks_fit, eks_fit_gaps or eks_ensemble_gaps -- and the strides, E and
+ * mode are ignored.  yev must be NULL or equal to obs (anything else is
+ * EKS_ERR_ARG); nothing is written to the planes.  A frame is complete iff
+ * every y and ev of it is finite.  On planes that eks_fit_gaps wrote from
+ * members, params, status, ncomplete and nkept are bit-identical to that call.
+ */
+
+/*
+ * eks_ensemble_gaps -- the ensemble over the VALID members of each column.
+ *
+ * Members are read as in eks_ensemble (strides in elements).  Member e of
+ * column (b, t, j) is valid iff it is finite: NaN, +inf and -inf are skipped.
+ * With m valid members and m >= min_members:
+ *     y  = nanmedian_e x  (EKS_MEDIAN: the middle valid value, or the mean of
+ *                          the two middle ones for even m)  or  nanmean_e x
+ *     ev = nanvar_e(x, ddof=0) / m        (eks_ensemble's "/ E" with the
+ *                                          count that was actually used)
+ * With m < min_members the column is missing: y = ev = NaN.  A column whose E
+ * members are all valid has the bits of eks_ensemble and of the planes eks_fit
+ * writes (E = 3, 4, 5, 8; another E agrees to an ulp of ev), so min_members =
+ * E is the all-members rule of eks_fit_gaps / eks_smooth_gaps.  min_members = 1 is
+ * allowed, but a single valid member gives ev = 0, which eks_smooth_gaps
+ * reports as an exact observation (EKS_STATUS_SCAN): use min_members >= 2.
+ *
+ * yev (required): EKS_YEV64 hand-off planes, eks_yev_bytes(B, T, n, EKS_F64,
+ * E, mode) bytes -- y float64 at [t*n + j][b], then ev float64 at the
+ * 256-byte aligned offset, exactly the layout eks_fit writes for EKS_YEV64
+ * (y is float64 whatever the members' type: an even m averages two members).
+ * eks_smooth_gaps, eks_nll_sweep_gaps and eks_fit_gaps read them with
+ * obs_dtype = EKS_YEV64.  nvalid (B T n bytes) or NULL: m of every column in
+ * the planes' layout [t*n + j][b].
+ * Limits: 1 <= n <= 64 and E <= eks_max_members(), else EKS_ERR_UNSUPPORTED.
+ * EKS_ERR_ARG (before any launch): NULL obs / yev, T < 1, E < 1, a bad dtype
+ * or mode, min_members outside [1, E].  B = 0: EKS_OK, nothing launched.
+ * No workspace; results are bit-reproducible.
+ */
+int eks_ensemble_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n,
+                      int64_t sb, int64_t st, int64_t se, int64_t sj, int mode, int min_members,
+                      void *yev, uint8_t *nvalid, void *stream);
 
 /*
  * eks_interp1d -- linear resampling for the asynchronous two-camera paw
