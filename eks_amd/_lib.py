@@ -95,6 +95,9 @@ SIGNATURES = {
                             _i32, C.c_double, C.c_double, _p, _p, _sz, _p, _p, _p, _p, _p]),
     "eks_ensemble_gaps": (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i32,
                                  _i32, _p, _p, _p]),
+    "eks_fit_pupil_workspace_bytes": (_sz, [_i64, _i64]),
+    "eks_fit_pupil": (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i32,
+                             _p, _p, _p, _sz, _p, _p, _p]),
     "eks_interp1d": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _p, _p]),
     "eks_debug_set": (_i64, [_i32, _i64]),
     "eks_profile_begin": (_i32, [_i32]),

@@ -489,6 +489,172 @@ def ensemble_gaps(obs, *, n: int, mode: str = "median", min_members: int,
     return dict(yev=yev, nvalid=nvalid)
 
 
+def fit_pupil(obs, *, mode: str = "median", check: bool = True, keep_yev=None):
+    """The statistics of the pupil model on the device (eks_fit_pupil): the
+    mean and population variance of the pupil diameter and centre over the
+    complete frames of every trajectory -- what ``fit.pupil_model`` derives
+    from ``preds[ok]`` with ok the frames whose ensemble average and variance
+    are finite in all 8 columns (``fit_gaps``'s rule; the reference's
+    nanmedian rescue of partly observed frames is not reproduced).
+
+    ``obs`` is a (B, T, E, 8) member view, float32 or float64, any strides,
+    columns in ``fit.PUPIL_KEYS`` order (a column is missing under the
+    all-members rule), or a ``Yev`` -- e.g. ``ensemble_gaps``'s, which is how a
+    ``min_members`` rule comes in: the fit then reads its planes, ``mode`` is
+    ignored, the returned ``yev`` is the one passed in and ``keep_yev`` must
+    be left unset.
+
+    ``keep_yev`` (member input): True, or a ``Yev`` whose buffer is reused
+    when it is large enough, also writes the ensemble planes (EKS_YEV64,
+    bit-identical to ``ensemble_gaps(min_members=E)``) that ``nll_sweep_gaps``
+    and ``smooth_gaps`` read in place of the members; unset: none are written.
+
+    Returns dict(stats (B, 6) float64 [mean diameter, mx, my, var diameter,
+    var com_x, var com_y], ncomplete (B,) int32, status (B,) int32, yev).
+    With ``check=True`` the call synchronises and raises ValueError when a
+    trajectory has no complete frame (EKS_STATUS_SINGULAR, NaN stats)."""
+    torch = _lib.require_gpu()
+    n = 8
+    from_yev = isinstance(obs, Yev)
+    if from_yev:
+        if keep_yev is not None:
+            raise ValueError("keep_yev cannot be combined with a Yev input: the planes are read, "
+                             "not written")
+        if obs.n != n:
+            raise ValueError(f"obs has {obs.n} coordinates, the pupil model has {n}")
+        B, T, E = obs.B, obs.T, obs.E
+        dt = obs.code
+        mode = obs.mode
+    else:
+        if obs.dim() != 4 or obs.shape[3] != n:
+            raise ValueError("obs must be viewed as (B, T, E, 8)")
+        B, T, E, _ = obs.shape
+        if obs.dtype not in (torch.float32, torch.float64):
+            raise TypeError("obs must be float32 or float64")
+        dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    lib = _lib.load()
+    dev = obs.device
+    m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
+    stats = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    ncomplete = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws = workspace(lib.eks_fit_pupil_workspace_bytes(B, T), dev, slot="fit_pupil")
+    if from_yev:
+        yev = obs
+        src, strides, yptr = obs.buf.data_ptr(), (0, 0, 0, 0), None
+    else:
+        yev = None
+        if keep_yev is not None and keep_yev is not False:
+            nbytes = lib.eks_yev_bytes(B, T, n, _lib.EKS_F64, E, m)
+            if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
+                yev = Yev(keep_yev.buf, B, T, E, n, _lib.EKS_YEV64, mode)
+            else:
+                yev = Yev(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), B, T, E, n,
+                          _lib.EKS_YEV64, mode)
+        src, strides = obs.data_ptr(), obs.stride()
+        yptr = yev.buf.data_ptr() if yev is not None else None
+    if B > 0:
+        _lib.check(lib.eks_fit_pupil(src, dt, B, T, E, n, *strides, m, stats.data_ptr(),
+                                     ncomplete.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     status.data_ptr(), yptr, _lib.stream_ptr()),
+                   "eks_fit_pupil")
+        if check:
+            bad = int((ncomplete == 0).sum().item())
+            if bad:
+                raise ValueError(f"eks_fit_pupil: {bad} of {B} trajectories have no complete "
+                                 "frame")
+    return dict(stats=stats, ncomplete=ncomplete, status=status, yev=yev)
+
+
+def pupil_params(stats, a_diag):
+    """``fit_pupil``'s statistics -> packed parameter rows of the pupil model
+    (n = 8, r = 3; eks/pupil_smoother.py:140-153), a pure function of torch
+    tensors on the device of ``stats`` like ``scale_q``.
+
+    ``stats`` is (B, 6); ``a_diag`` the diagonals of K candidate transition
+    matrices, (K, 3) shared by all trajectories or (K, B, 3).  Returns
+    (K * B, P) float64 rows, row k * B + b candidate k of trajectory b (the
+    ``nll_sweep_gaps`` convention): m0 = [mean d, 0, 0], S0 = diag(var),
+    A = diag(a), Q = diag(var (1 - a^2)), C the pupil matrix,
+    offset = [mx, my] x 4."""
+    import torch
+    stats = torch.as_tensor(stats, dtype=torch.float64)
+    if stats.dim() != 2 or stats.shape[1] != 6:
+        raise ValueError("stats must be (B, 6)")
+    B = stats.shape[0]
+    if not isinstance(a_diag, torch.Tensor):
+        a_diag = np.array(a_diag, dtype=np.float64)  # (a copy: views may be read-only)
+    a = torch.as_tensor(a_diag, dtype=torch.float64).to(stats.device)
+    if a.dim() == 2:
+        a = a.unsqueeze(1).expand(-1, B, -1)
+    if a.dim() != 3 or a.shape[1:] != (B, 3):
+        raise ValueError(f"a_diag must be (K, 3) or (K, {B}, 3)")
+    K = a.shape[0]
+    r, n = 3, 8
+    var = stats[:, 3:6].unsqueeze(0).expand(K, B, 3)
+    q = var * (1 - a ** 2)
+    rows = torch.zeros((K, B, param_len(n, r)), dtype=torch.float64, device=stats.device)
+    rows[:, :, 0] = stats[:, 0]
+    s0, a0, q0, c0 = r, r + r * r, r + 2 * r * r, r + 3 * r * r
+    for i in range(r):
+        rows[:, :, s0 + i * (r + 1)] = var[:, :, i]
+        rows[:, :, a0 + i * (r + 1)] = a[:, :, i]
+        rows[:, :, q0 + i * (r + 1)] = q[:, :, i]
+    rows[:, :, c0:c0 + n * r] = torch.as_tensor(_PUPIL_C.reshape(-1), device=stats.device)
+    rows[:, :, c0 + n * r:] = stats[:, 1:3].repeat(1, 4)
+    return rows.view(K * B, -1)
+
+
+def pupil_sweep(obs, diameter_s_grid, com_s_grid, *, mode: str = "median", min_members=None,
+                want_var: bool = False):
+    """The pupil smoother with its two smoothing parameters chosen by
+    likelihood, members -> fit -> sweep -> smooth without a member or a plane
+    leaving the device.
+
+    ``obs`` is a (B, T, E, 8) member view (or a ``Yev``).  With
+    ``min_members`` the ensemble is ``ensemble_gaps``'s over the finite members
+    of each column.  ``fit_pupil`` gives the statistics, ``pupil_params`` the
+    K = len(diameter_s_grid) * len(com_s_grid) candidate rows per trajectory
+    (A = diag(d, c, c), diameter-major), ``nll_sweep_gaps`` scores them over
+    the observed entries, each trajectory takes its first minimum in grid
+    order and ``smooth_gaps`` runs with the chosen rows.
+
+    Returns dict(best (B, 2) the chosen (d, c), nll (K, B), params (B, P),
+    stats, ncomplete, nobs (B,) observed entries, out (B, T, 8), ms (B, T, 3),
+    var (B, T, 8) with ``want_var`` else None, status (B,) int32: the fit's,
+    the sweep's (over the candidates) and the smoother's bits)."""
+    torch = _lib.require_gpu()
+    n, r = 8, 3
+    if min_members is not None:
+        if isinstance(obs, Yev):
+            raise ValueError("min_members needs the members, not their planes")
+        obs = ensemble_gaps(obs, n=n, mode=mode, min_members=min_members)["yev"]
+    f = fit_pupil(obs, mode=mode, check=True, keep_yev=None if isinstance(obs, Yev) else True)
+    yev = f["yev"]
+    dev = yev.device
+    B = yev.B
+    d = torch.as_tensor(np.asarray(diameter_s_grid, dtype=np.float64), device=dev).flatten()
+    c = torch.as_tensor(np.asarray(com_s_grid, dtype=np.float64), device=dev).flatten()
+    if d.numel() < 1 or c.numel() < 1:
+        raise ValueError("the grids must not be empty")
+    grid = torch.cartesian_prod(d, c).reshape(-1, 2)  # diameter-major
+    K = grid.shape[0]
+    rows = pupil_params(f["stats"], torch.stack([grid[:, 0], grid[:, 1], grid[:, 1]], 1))
+    sw = nll_sweep_gaps(yev, rows, K=K, n=n, r=r, mode=yev.mode)
+    idx = torch.argmin(sw["nll"], dim=0)  # the first minimum in grid order
+    params = rows.view(K, B, -1)[idx, torch.arange(B, device=dev)].contiguous()
+    sm = smooth_gaps(yev, params, n=n, r=r, mode=yev.mode, want_ms=True, want_var=want_var,
+                     check=True)
+    status = f["status"] | sm["status"]
+    for bit in (_lib.EKS_STATUS_SINGULAR, _lib.EKS_STATUS_BAD_MODEL, _lib.EKS_STATUS_SCAN):
+        status = status | ((sw["status"] & bit) != 0).any(dim=0).to(torch.int32) * bit
+    return dict(best=grid[idx], nll=sw["nll"], params=params, stats=f["stats"],
+                ncomplete=f["ncomplete"], nobs=sm["nobs"], out=sm["out"], ms=sm["ms"],
+                var=sm["var"], status=status)
+
+
 def nll(obs, params, *, n: int, r: int, mode: str = "median", flags: int = 0, algo: int = 0,
         check: bool = True, status=None):
     """Filter-only pass: the innovation NLL of every

@@ -23,6 +23,7 @@
 //   eks::fit(obs, kind, n, r, s, q, mode)          eks/multiview_pca_smoother.py:684-731
 //   eks::fit_gaps(obs, kind, n, r, s, q, mode)     the same through missing observations
 //   eks::ensemble_gaps(obs, mode, min_members)     the ensemble over the valid members
+//   eks::fit_pupil(obs, mode)                      the pupil model's statistics (complete frames)
 //   eks::newton_filter(y, ev, mu0, S0, A, Bm, E, max_iter)  eks/newton_eks.py:115-148
 //   eks::interp1d(x, y, xq)                        eks/multiview_pca_smoother.py:86-96
 #include <ATen/ATen.h>
@@ -500,6 +501,40 @@ std::tuple<Tensor, Tensor> ensemble_gaps_meta(const Tensor& obs, const std::stri
           at::empty({T, n, B}, obs.options().dtype(at::kByte))};
 }
 
+// --------------------------------------------------------------- fit_pupil
+// (stats (B, 6), ncomplete, status, yev bytes: the EKS_YEV64 planes of
+// eks_ensemble_gaps(min_members = E))
+using FitPupil = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+FitPupil fit_pupil_gpu(const Tensor& obs, const std::string& mode) {
+  need_gpu(obs, "obs");
+  TORCH_CHECK(obs.dim() == 4 && obs.size(3) == 8, "obs must be viewed as (B, T, E, 8)");
+  const c10::DeviceGuard g(obs.device());
+  const int64_t B = obs.size(0), T = obs.size(1), E = obs.size(2);
+  Tensor stats = at::empty({B, 6}, f64(obs));
+  Tensor ncomplete = at::empty({B}, i32(obs));
+  Tensor status = at::empty({B}, i32(obs));
+  const size_t yb = eks_yev_bytes(B, T, 8, EKS_F64, (int)E, mode_code(mode));
+  Tensor yev = at::empty({(int64_t)yb}, obs.options().dtype(at::kByte));
+  const size_t wsb = eks_fit_pupil_workspace_bytes(B, T);
+  Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 1)}, obs.options().dtype(at::kByte));
+  if (B > 0)  // (an empty batch has no planes to point at)
+    check(eks_fit_pupil(obs.data_ptr(), obs_dtype(obs), B, T, (int)E, 8, obs.stride(0),
+                        obs.stride(1), obs.stride(2), obs.stride(3), mode_code(mode),
+                        stats.data_ptr<double>(), ncomplete.data_ptr<int32_t>(), ws.data_ptr(),
+                        (size_t)ws.numel(), status.data_ptr<int32_t>(), yev.data_ptr(),
+                        cur_stream(obs)),
+          "eks_fit_pupil");
+  return {stats, ncomplete, status, yev};
+}
+FitPupil fit_pupil_meta(const Tensor& obs, const std::string& mode) {
+  TORCH_CHECK(obs.dim() == 4 && obs.size(3) == 8, "obs must be viewed as (B, T, E, 8)");
+  const auto i32o = obs.options().dtype(at::kInt);
+  const int64_t B = obs.size(0);
+  const size_t yb = eks_yev_bytes(B, obs.size(1), 8, EKS_F64, (int)obs.size(2), mode_code(mode));
+  return {at::empty({B, 6}, obs.options().dtype(at::kDouble)), at::empty({B}, i32o),
+          at::empty({B}, i32o), at::empty({(int64_t)yb}, obs.options().dtype(at::kByte))};
+}
+
 // ---------------------------------------------------------- newton_filter
 std::tuple<Tensor, Tensor> newton_gpu(const Tensor& y, const Tensor& ev, const Tensor& mu0,
                                       const Tensor& S0, const Tensor& A, const Tensor& Bm,
@@ -578,6 +613,8 @@ TORCH_LIBRARY(eks, m) {
   m.def("fit_gaps(Tensor obs, str kind, int n, int r, float smooth_param, float quantile_keep, "
         "str mode) -> (Tensor params, Tensor status, Tensor yev, Tensor ncomplete, Tensor nkept)");
   m.def("ensemble_gaps(Tensor obs, str mode, int min_members) -> (Tensor, Tensor)");
+  m.def("fit_pupil(Tensor obs, str mode) -> "
+        "(Tensor stats, Tensor ncomplete, Tensor status, Tensor yev)");
   m.def("newton_filter(Tensor y, Tensor ev, Tensor mu0, Tensor S0, Tensor A, Tensor Bm, "
         "Tensor E, int max_iter) -> (Tensor, Tensor)");
   m.def("interp1d(Tensor x, Tensor y, Tensor xq) -> Tensor");
@@ -596,6 +633,7 @@ TORCH_LIBRARY_IMPL(eks, CUDA, m) {
   m.impl("fit", &fit_gpu);
   m.impl("fit_gaps", &fit_gaps_gpu);
   m.impl("ensemble_gaps", &ensemble_gaps_gpu);
+  m.impl("fit_pupil", &fit_pupil_gpu);
   m.impl("newton_filter", &newton_gpu);
   m.impl("interp1d", &interp_gpu);
 }
@@ -613,6 +651,7 @@ TORCH_LIBRARY_IMPL(eks, Meta, m) {
   m.impl("fit", &fit_meta);
   m.impl("fit_gaps", &fit_gaps_meta);
   m.impl("ensemble_gaps", &ensemble_gaps_meta);
+  m.impl("fit_pupil", &fit_pupil_meta);
   m.impl("newton_filter", &newton_meta);
   m.impl("interp1d", &interp_meta);
 }

@@ -31,6 +31,9 @@ CPU tensor is a dispatch error).  Layout conventions are those of
     ensemble_gaps (obs, mode, min_members) -> (yev bytes (EKS_YEV64 planes), nvalid (T,n,B) uint8):
                the ensemble over the finite members of each column, missing only where
                fewer than min_members are finite
+    fit_pupil  (obs (B,T,E,8), mode) -> (stats (B,6), ncomplete (B), status (B), yev bytes):
+               the pupil model's statistics over the complete frames, and the EKS_YEV64
+               ensemble planes of eks_ensemble_gaps(min_members=E)
 """
 from __future__ import annotations
 
@@ -43,7 +46,8 @@ from . import _lib
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libeks_torch.so")
 
 OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "smooth_gaps", "nll",
-       "nll_sweep", "nll_sweep_gaps", "fit", "fit_gaps", "ensemble_gaps", "newton_filter", "interp1d")
+       "nll_sweep", "nll_sweep_gaps", "fit", "fit_gaps", "ensemble_gaps", "fit_pupil", "newton_filter",
+       "interp1d")
 
 
 def _load():

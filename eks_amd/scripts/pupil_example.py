@@ -9,7 +9,8 @@ opti:     opti_eks_pupil_traces.csv + opti_eks_latents.csv;
 plus example_eks_result.pdf (skip with --no-plot).  Additive option
 --sweep D1,D2,... C1,C2,...: choose (diameter_s, com_s) from the grid by
 innovation likelihood (eks_amd.smoothers.pupil_smoothing_sweep, one batched
-filter-only GPU call) instead of taking --diameter-s/--com-s.
+filter-only GPU call) instead of taking --diameter-s/--com-s.  --device-fit:
+fit the pupil model on the device too (fit_on_device=True; standard only).
 """
 from __future__ import annotations
 
@@ -33,6 +34,8 @@ def build_parser():
                    help='choose eks version: "opti" (Newton filter) or anything else (standard)')
     p.add_argument('--sweep', nargs=2, default=None, metavar=('DIAMETER_S_LIST', 'COM_S_LIST'),
                    help='comma-separated grids; pick the pair with the lowest NLL (standard only)')
+    p.add_argument('--device-fit', action='store_true',
+                   help='fit the pupil model on the device (standard only)')
     p.add_argument('--no-plot', action='store_true', help='do not write the example plot')
     return p
 
@@ -56,13 +59,14 @@ def run(args):
         d = eks_opti_smoother_pupil(state_transition_matrix=A, **kw)
         names = ('opti_eks_pupil_traces.csv', 'opti_eks_latents.csv')
     else:
+        dev = dict(fit_on_device=True) if args.device_fit else {}
         if args.sweep:
             dg = [float(x) for x in args.sweep[0].split(',')]
             cg = [float(x) for x in args.sweep[1].split(',')]
-            d = pupil_smoothing_sweep(markers_list, keypoint_names, TRACKER, dg, cg)
+            d = pupil_smoothing_sweep(markers_list, keypoint_names, TRACKER, dg, cg, **dev)
             print(f'chosen (diameter_s, com_s) = {d["best"]}')
         else:
-            d = ensemble_kalman_smoother_pupil(state_transition_matrix=A, **kw)
+            d = ensemble_kalman_smoother_pupil(state_transition_matrix=A, **kw, **dev)
         names = ('kalman_smoothed_pupil_traces.csv', 'kalman_smoothed_latents.csv')
     files = []
     for key, name in zip(('markers_df', 'latents_df'), names):

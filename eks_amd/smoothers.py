@@ -175,9 +175,77 @@ def _run_gaps_pupil(yev, model: dict, pv: bool):
             res["Vs"][0].cpu().numpy() if pv else None, T * n - int(res["nobs"][0].item()))
 
 
+def _pupil_device_obs(stack, min_members):
+    """(E, T, 8) host members -> what batch.fit_pupil / batch.pupil_sweep read
+    on the device: the (1, T, E, 8) member view, uploaded once, or with
+    ``min_members`` the planes of batch.ensemble_gaps."""
+    torch = _lib.require_gpu()
+    obs = torch.from_numpy(np.ascontiguousarray(stack, dtype=np.float64)).to("cuda")
+    obs = obs.permute(1, 0, 2).unsqueeze(0)  # (1, T, E, 8) view, no copy
+    if min_members is not None:
+        return batch.ensemble_gaps(obs, n=obs.shape[3], min_members=min_members)["yev"]
+    return obs
+
+
+def _check_device_complete(ncomplete, T, allow_missing):
+    """allow_missing=False promises members without gaps to the device fit."""
+    m = int(ncomplete[0].item())
+    if not allow_missing and m < T:
+        raise ValueError(f"the device fit found {T - m} of {T} frames with a missing or "
+                         "non-finite prediction: pass allow_missing=True to fit on the "
+                         "complete frames and smooth through the gaps")
+
+
+def _pupil_dfs(out, ms, mx, my, keypoint_names, tracker_name, var=None, Vs=None):
+    """The pupil wrappers' DataFrames from out (T, 8), ms (T, 3) and, for the
+    posterior variances, var (T, 8) and Vs (T, 3, 3)."""
+    nan = np.full(out.shape[0], np.nan)
+
+    def markers(arr):
+        by_key = {k: arr[:, j] for j, k in enumerate(fit.PUPIL_KEYS)}
+        cols = []
+        for kp in ('top', 'right', 'bottom', 'left'):  # output order of :199-203
+            cols += [by_key[f'pupil_{kp}_r_x'], by_key[f'pupil_{kp}_r_y'], nan]
+        return pd.DataFrame(np.stack(cols, 1), columns=make_dlc_pandas_index(keypoint_names))
+
+    lat = np.stack([ms[:, 0], ms[:, 1] + mx, ms[:, 2] + my], 1)
+    idx = pd.MultiIndex.from_arrays([[tracker_name] * 3, ['diameter', 'com_x', 'com_y']],
+                                    names=('scorer', 'latent'))
+    res = {'markers_df': markers(out), 'latents_df': pd.DataFrame(lat, columns=idx)}
+    if var is not None:
+        res['posterior_var_df'] = markers(var)
+        res['latents_posterior_var_df'] = pd.DataFrame(
+            np.diagonal(Vs, axis1=1, axis2=2).copy(), columns=idx)
+    return res
+
+
+def _pupil_on_device(stack, keypoint_names, tracker_name, state_transition_matrix, pv,
+                     allow_missing, min_members):
+    """ensemble_kalman_smoother_pupil(fit_on_device=True): members -> fit ->
+    smooth on the device; only the results come back."""
+    A = np.asarray(state_transition_matrix, dtype=np.float64)
+    if A.shape != (3, 3) or not batch._diagonal(A):
+        raise ValueError("fit_on_device=True needs a diagonal 3 x 3 state_transition_matrix")
+    T = stack.shape[1]
+    obs = _pupil_device_obs(stack, min_members)
+    f = batch.fit_pupil(obs, keep_yev=None if isinstance(obs, batch.Yev) else True)
+    _check_device_complete(f["ncomplete"], T, allow_missing)
+    params = batch.pupil_params(f["stats"], np.diag(A)[None])
+    sm = batch.smooth_gaps(f["yev"], params, n=8, r=3, want_ms=True, want_var=pv, want_Vs=pv,
+                           check=True)
+    stats = f["stats"][0].cpu().numpy()
+    res = _pupil_dfs(sm["out"][0].cpu().numpy(), sm["ms"][0].cpu().numpy(), stats[1], stats[2],
+                     keypoint_names, tracker_name,
+                     sm["var"][0].cpu().numpy() if pv else None,
+                     sm["Vs"][0].cpu().numpy() if pv else None)
+    if allow_missing:
+        res['n_missing'] = T * 8 - int(sm["nobs"][0].item())
+    return res
+
+
 def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
                                    state_transition_matrix, posterior_var=False,
-                                   allow_missing=False, min_members=None):
+                                   allow_missing=False, min_members=None, fit_on_device=False):
     """IBL pupil smoother (eks/pupil_smoother.py:82-223).
 
     ``allow_missing=True``: a column whose ensemble average or variance is not
@@ -191,10 +259,19 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
     Returns {'markers_df': smoothed keypoints in the order top, right, bottom,
     left (NaN likelihood), 'latents_df': diameter, com_x, com_y}.  With
     ``posterior_var`` also 'posterior_var_df' (the markers layout, x / y holding
-    the posterior variances) and 'latents_posterior_var_df' (diag(Vs))."""
+    the posterior variances) and 'latents_posterior_var_df' (diag(Vs)).
+
+    ``fit_on_device=True``: the members go to the device once, the model comes
+    from batch.fit_pupil + batch.pupil_params instead of the host fit, and the
+    smoother reads the planes the fit wrote (batch.smooth_gaps); the dict has
+    the same keys.  Without ``allow_missing`` a frame the device fit finds
+    incomplete raises ValueError."""
     _check_min_members(min_members, allow_missing)
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
+    if fit_on_device:
+        return _pupil_on_device(stack, keypoint_names, tracker_name, state_transition_matrix,
+                                bool(posterior_var), allow_missing, min_members)
     yev, preds, ev = core.ensemble_handoff(stack, min_members=min_members)
     pv = bool(posterior_var)
     n_missing = None
@@ -205,31 +282,16 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
         model = fit.pupil_model(preds, state_transition_matrix)
         out, ms, _, *var_Vs = _run_fused(stack, model, want_ms=True, yev=yev, want_var=pv,
                                          want_Vs=pv)
-    nan = np.full(out.shape[0], np.nan)
-
-    def markers(arr):
-        by_key = {k: arr[:, j] for j, k in enumerate(fit.PUPIL_KEYS)}
-        cols = []
-        for kp in ('top', 'right', 'bottom', 'left'):  # output order of :199-203
-            cols += [by_key[f'pupil_{kp}_r_x'], by_key[f'pupil_{kp}_r_y'], nan]
-        return pd.DataFrame(np.stack(cols, 1), columns=make_dlc_pandas_index(keypoint_names))
-
-    lat = np.stack([ms[:, 0], ms[:, 1] + model["mx"], ms[:, 2] + model["my"]], 1)
-    idx = pd.MultiIndex.from_arrays([[tracker_name] * 3, ['diameter', 'com_x', 'com_y']],
-                                    names=('scorer', 'latent'))
-    res = {'markers_df': markers(out), 'latents_df': pd.DataFrame(lat, columns=idx)}
+    var, Vs = var_Vs if pv else (None, None)
+    res = _pupil_dfs(out, ms, model["mx"], model["my"], keypoint_names, tracker_name, var, Vs)
     if allow_missing:
         res['n_missing'] = n_missing
-    if pv:
-        var, Vs = var_Vs
-        res['posterior_var_df'] = markers(var)
-        res['latents_posterior_var_df'] = pd.DataFrame(
-            np.diagonal(Vs, axis1=1, axis2=2).copy(), columns=idx)
     return res
 
 
 def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s_grid,
-                          com_s_grid, allow_missing=False, min_members=None):
+                          com_s_grid, allow_missing=False, min_members=None,
+                          fit_on_device=False):
     """The pupil smoother with its smoothing parameters chosen by likelihood.
 
     Every (diameter_s, com_s) pair of the grid defines a model
@@ -244,12 +306,29 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
     (they share C and offset and differ in A and Q), scored over the observed
     entries in one batch.nll_sweep_gaps call, and the argmin is smoothed
     through the gaps (ensemble_kalman_smoother_pupil(allow_missing=True));
-    ``min_members`` as there."""
+    ``min_members`` as there.
+
+    ``fit_on_device=True``: the members go to the device once and
+    batch.pupil_sweep fits, scores, picks and smooths there (the gaps kernels,
+    from the planes); the dict has the same keys.  Without ``allow_missing`` a
+    frame the device fit finds incomplete raises ValueError."""
     _check_min_members(min_members, allow_missing)
     torch = _lib.require_gpu()
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
     E, T, n = stack.shape
+    if fit_on_device:
+        sw = batch.pupil_sweep(_pupil_device_obs(stack, min_members), diameter_s_grid,
+                               com_s_grid)
+        _check_device_complete(sw["ncomplete"], T, allow_missing)
+        stats = sw["stats"][0].cpu().numpy()
+        res = _pupil_dfs(sw["out"][0].cpu().numpy(), sw["ms"][0].cpu().numpy(), stats[1],
+                         stats[2], keypoint_names, tracker_name)
+        if allow_missing:
+            res["n_missing"] = T * n - int(sw["nobs"][0].item())
+        res["nll"] = sw["nll"][:, 0].cpu().numpy().reshape(len(diameter_s_grid), len(com_s_grid))
+        res["best"] = tuple(float(v) for v in sw["best"][0].cpu().numpy())
+        return res
     if allow_missing:
         yev, preds, ev = core.ensemble_handoff(stack, min_members=min_members)
         ok = _complete_frames(preds, ev)

@@ -566,6 +566,51 @@ int eks_ensemble_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int 
                       void *yev, uint8_t *nvalid, void *stream);
 
 /*
+ * eks_fit_pupil -- the statistics of the pupil model (eks/pupil_smoother.py:
+ * 109-172) on the device, for B trajectories at once: the mean and population
+ * variance (ddof 0) of the pupil diameter and of the pupil centre over the
+ * complete frames.
+ *
+ *   obs      member observations, strides as eks_ensemble (EKS_F32 / EKS_F64),
+ *            columns in the order top x, y, bottom x, y, right x, y, left x, y;
+ *            or y / ev hand-off planes for (B, T, 8) (EKS_YEV32 / EKS_YEV64, as
+ *            eks_fit_gaps accepts: the strides, E and mode are then ignored and
+ *            yev must be NULL)
+ *   n        must be 8, else EKS_ERR_UNSUPPORTED; T >= 2; E <= eks_max_members()
+ *   stats    (B, 6) float64: mean diameter, mean centre x, y, var diameter,
+ *            var centre x, y
+ *   ncomplete (B) int32, REQUIRED: the complete frames
+ *   status   (B) int32, REQUIRED; zeroed by the call.  A trajectory without a
+ *            complete frame: EKS_STATUS_SINGULAR, ncomplete 0, NaN stats (the
+ *            other trajectories are unaffected); exactly one complete frame:
+ *            variances exactly 0
+ *   yev      NULL, or (member input only) eks_yev_bytes(B, T, 8, EKS_F64, E,
+ *            mode) bytes: the ensemble planes, always EKS_YEV64, bit-identical
+ *            to eks_ensemble_gaps(min_members = E) on the same members -- what
+ *            eks_nll_sweep_gaps / eks_smooth_gaps read, so the members are read
+ *            once for fit + sweep + smooth
+ *
+ * A frame is complete iff the ensemble average and variance of all 8 columns
+ * are finite (eks_fit_gaps's rule); from members a column is missing under the
+ * all-members rule, and a min_members rule comes in through the planes of
+ * eks_ensemble_gaps.  Only complete frames enter the statistics: the
+ * reference's nanmedian rescue of partly observed frames is deliberately not
+ * reproduced (this is the host fit on preds[ok]).  Per complete frame the
+ * diameter is the median of the six estimates (top-bottom, left-right, the
+ * four neighbour pairs x sqrt 2), the centre the mean of the two pair
+ * midpoints per coordinate.  No floating-point atomics: results are
+ * bit-identical from run to run.
+ * EKS_ERR_ARG before any launch: a NULL pointer, a bad dtype or mode, T < 2,
+ * E < 1, a workspace below eks_fit_pupil_workspace_bytes (0 for B <= 0 or
+ * T < 2).  B = 0: EKS_OK, nothing launched.
+ */
+size_t eks_fit_pupil_workspace_bytes(int64_t B, int64_t T);
+int eks_fit_pupil(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n,
+                  int64_t sb, int64_t st, int64_t se, int64_t sj, int mode, double *stats,
+                  int32_t *ncomplete, void *workspace, size_t workspace_bytes, int32_t *status,
+                  void *yev, void *stream);
+
+/*
  * eks_interp1d -- linear resampling for the asynchronous two-camera paw
  * smoother (F4), replacing the scipy.interpolate.interp1d(kind='linear')
  * calls of eks/multiview_pca_smoother.py:86-96 (which delegate to np.interp
