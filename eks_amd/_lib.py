@@ -30,6 +30,7 @@ EKS_DBG_PVAR_CHUNK = 7
 EKS_DBG_SWEEP_CHUNK = 8
 EKS_DBG_GAPS_CHUNK = 9
 EKS_DBG_GAPS_SWEEP_CHUNK = 10
+EKS_DBG_DRAWS_RAW = 11
 # eks_smooth_plan_info: index of every value (EKS_PLAN_* in the header), and their names
 (EKS_PLAN_ALGO, EKS_PLAN_L, EKS_PLAN_NC, EKS_PLAN_LS, EKS_PLAN_UNIFORM, EKS_PLAN_WAVE_SCAN,
  EKS_PLAN_GRP, EKS_PLAN_JD, EKS_PLAN_G, EKS_PLAN_NG, EKS_PLAN_FINE_LEN, EKS_PLAN_NCF,
@@ -74,6 +75,12 @@ SIGNATURES = {
     "eks_smooth_gaps_chunk_len": (_i64, [_i64, _i64, _i32]),
     "eks_smooth_gaps": (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32,
                                _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "eks_draws_gaps_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
+    "eks_draws_gaps_chunk_len": (_i64, [_i64, _i64, _i32]),
+    "eks_draws_gaps": (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32,
+                              _p, _i64, _p, _i64, _i64, _i64, C.c_uint64, _p, _i64, _i64, _i64,
+                              _i64, _p, _p, _i64, _i64, _i64, _p, _p, _sz, _p, _p]),
+    "eks_draws_noise": (_i32, [_i64, _i64, _i64, _i32, C.c_uint64, _p, _i64, _i64, _i64, _p]),
     "eks_nll_sweep_gaps_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
     "eks_nll_sweep_gaps_chunk_len": (_i64, [_i64, _i64, _i64, _i32]),
     "eks_nll_sweep_gaps": (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64,

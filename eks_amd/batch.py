@@ -800,6 +800,102 @@ def smooth_gaps(obs, params, *, n: int, r: int, mode: str = "median", want_var: 
     return dict(out=out, var=var, Vs=Vs, ms=ms, nll=nll_, nobs=nobs, status=status)
 
 
+def draws_noise(B: int, S: int, T: int, r: int, seed: int, device="cuda", stream=None):
+    """The noise z(b, s, t, i) that ``draws_gaps(seed=seed)`` generates in its
+    kernels (eks_draws_noise; the generator's layout is in include/eks_hip.h):
+    a (B, S, T, r) float64 view of a time-major (T, B, S, r) buffer."""
+    torch = _lib.require_gpu()
+    z = torch.empty((T, B, S, r), dtype=torch.float64, device=device).permute(1, 2, 0, 3)
+    zb, zs, zt, _ = z.stride()
+    _lib.check(_lib.load().eks_draws_noise(B, S, T, r, int(seed) & (2 ** 64 - 1), z.data_ptr(),
+                                           zb, zs, zt, _lib.stream_ptr(stream)),
+               "eks_draws_noise")
+    return z
+
+
+def _dummy_buffer(torch, dev):
+    """A one-element device buffer for a required pointer that is never used."""
+    return workspace(8, dev, slot="dummy")
+
+
+def draws_gaps(obs, params, *, n: int, r: int, S=None, noise=None, seed=None,
+               mode: str = "median", want_latent: bool = False, want_out: bool = True,
+               want_var: bool = False, check: bool = False, status=None, stream=None):
+    """S joint draws per trajectory from the smoothing posterior of
+    ``smooth_gaps`` (eks_draws_gaps), same inputs and missing rule: consecutive
+    frames of a draw are correlated as the posterior is, so a statistic that
+    spans frames (speed, path length, time above a threshold) gets its error
+    bar from the draws.
+
+    Exactly one of ``noise`` -- a (B, S, T, r) float64 tensor of standard
+    normals with a contiguous last axis, ``draws_noise``'s layout for coalesced
+    loads -- and ``seed`` (with ``S``; the kernels generate the noise, none is
+    allocated) is given.
+
+    Returns dict(draws=(B,S,T,n) view of a (T,B,S,n) buffer, latent=(B,S,T,r)
+    or None, out and var as ``smooth_gaps`` (None unless asked), status=(B,)
+    int32).  A trajectory with a non-positive Cholesky pivot has
+    EKS_STATUS_SINGULAR and NaN draws.  ``check=True`` as in ``smooth_gaps``."""
+    if (noise is None) == (seed is None):
+        raise ValueError("draws_gaps needs exactly one of noise and seed")
+    torch = _lib.require_gpu()
+    B, T, E, dt = _obs_code(obs, n)
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    yev = isinstance(obs, Yev)
+    if yev and mode != obs.mode:
+        raise ValueError("the hand-off planes were made in another averaging mode")
+    if params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
+            or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    if noise is not None:
+        if noise.dim() != 4 or noise.shape[0] != B or noise.shape[2:] != (T, r) \
+                or noise.dtype != torch.float64 or (r > 1 and noise.stride(3) != 1):
+            raise ValueError(f"noise must be a ({B}, S, {T}, {r}) float64 tensor with a "
+                             "contiguous last axis")
+        if S is not None and S != noise.shape[1]:
+            raise ValueError(f"S={S} but noise holds {noise.shape[1]} draws")
+        S = noise.shape[1]
+        zb, zs, zt, _ = noise.stride()
+    else:
+        if S is None or S < 0:
+            raise ValueError("draws_gaps(seed=...) needs S >= 0")
+        zb = zs = zt = 0
+    dev = obs.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    draws = torch.empty((T, B, S, n), **f64).permute(1, 2, 0, 3)
+    # (S = 0: an empty tensor has no storage; the entry point wants a pointer it never touches)
+    draws_ptr = draws.data_ptr() or _dummy_buffer(torch, dev).data_ptr()
+    latent = torch.empty((B, S, T, r), **f64) if want_latent else None
+    out = torch.empty((T, B, n), **f64).permute(1, 0, 2) if want_out or want_var else None
+    var = torch.empty((T, B, n), **f64).permute(1, 0, 2) if want_var else None
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = workspace(lib.eks_draws_gaps_workspace_bytes(B, S, T, n, r), dev, slot="draws_gaps")
+    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
+    db, ds, dtt, dj = draws.stride()
+    ob, ot, oj = out.stride() if out is not None else (0, 0, 0)
+
+    def ptr(x):
+        return x.data_ptr() if x is not None else None
+
+    _lib.check(lib.eks_draws_gaps(
+        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
+        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(),
+        S, ptr(noise), zb, zs, zt, (int(seed) & (2 ** 64 - 1)) if seed is not None else 0,
+        draws_ptr, db, ds, dtt, dj, ptr(latent), ptr(out), ob, ot, oj, ptr(var),
+        ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)), "eks_draws_gaps")
+    if check and B > 0:
+        bits = status_bits(status)
+        if bits & _lib.EKS_STATUS_SCAN:
+            raise ValueError("an observed column with zero ensemble variance: eks_draws_gaps "
+                             "does not serve it")
+        if bits & _lib.EKS_STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+    return dict(draws=draws, latent=latent, out=out if want_out else None, var=var, status=status)
+
+
 def nll_sweep_gaps(obs, params, *, K: int, n: int, r: int, mode: str = "median",
                    check: bool = True, status=None, stream=None):
     """``nll_sweep`` through missing observations (eks_nll_sweep_gaps): the

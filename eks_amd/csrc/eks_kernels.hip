@@ -650,7 +650,7 @@ using namespace eks;
 extern "C" {
 
 const char *eks_last_error(void) { return g_err.c_str(); }
-int eks_version(void) { return 107; }
+int eks_version(void) { return 108; }
 int eks_max_latent(void) { return kMaxLatent; }
 int eks_max_obs(void) { return kMaxObs; }
 int eks_max_members(void) { return kMaxMembers; }

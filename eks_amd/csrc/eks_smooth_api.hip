@@ -49,6 +49,7 @@ extern long long g_pvar_chunk;  // eks_postvar.hip
 extern long long g_sweep_chunk;  // eks_sweep.hip
 extern long long g_gaps_chunk;   // eks_gaps.hip
 extern long long g_gaps_sweep_chunk;  // eks_gaps_sweep.hip
+extern long long g_draws_raw;         // eks_draws_gaps.hip
 }
 
 extern "C" {
@@ -278,6 +279,11 @@ int64_t eks_debug_set(int key, int64_t value) {
     case EKS_DBG_GAPS_SWEEP_CHUNK: {
       const long long prev = g_gaps_sweep_chunk;
       g_gaps_sweep_chunk = value > 0 ? value : 0;
+      return prev;
+    }
+    case EKS_DBG_DRAWS_RAW: {
+      const long long prev = g_draws_raw;
+      g_draws_raw = value != 0 ? 1 : 0;
       return prev;
     }
     default: return set_err(EKS_ERR_ARG, "eks_debug_set: unknown key %d", key), -1;

@@ -18,6 +18,8 @@
 //   eks::smooth(obs, params, n, r, mode, flags, algo)  the fused hot path
 //   eks::smooth_var(obs, params, n, r)             posterior variances of smooth's output
 //   eks::smooth_gaps(obs, params, n, r, mode)      the smoother through missing observations
+//   eks::draws_gaps(obs, params, noise, n, r, mode)  joint posterior draws from given noise
+//   eks::draws_noise(like, B, S, T, r, seed)       the noise of a seeded draws call
 //   eks::nll_sweep(obs, params, K, n, r, mode)     the NLL of K candidate models per trajectory
 //   eks::nll_sweep_gaps(obs, params, K, n, r, mode)  the same through missing observations
 //   eks::fit(obs, kind, n, r, s, q, mode)          eks/multiview_pca_smoother.py:684-731
@@ -315,6 +317,69 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> smooth_gaps_meta(const Tensor
   return {at::empty({obs.size(0), obs.size(1), n}, o), at::empty({obs.size(0), obs.size(1), n}, o),
           at::empty({obs.size(0)}, o), at::empty({obs.size(0)}, i), at::empty({obs.size(0)}, i)};
 }
+// joint posterior draws through missing observations from the caller's noise
+// (B, S, T, r): draws (B, S, T, n), latent (B, S, T, r), out (B, T, n), status (B)
+std::tuple<Tensor, Tensor, Tensor, Tensor> draws_gaps_gpu(const Tensor& obs, const Tensor& params,
+                                                          const Tensor& noise, int64_t n,
+                                                          int64_t r, const std::string& mode) {
+  need_gpu(obs, "obs");
+  need_gpu(params, "params");
+  need_gpu(noise, "noise");
+  TORCH_CHECK(params.device() == obs.device() && noise.device() == obs.device(),
+              "obs, params and noise must be on one device");
+  TORCH_CHECK(obs.dim() == 4 && obs.size(3) == n, "obs must be viewed as (B, T, E, n) with n=", n);
+  const c10::DeviceGuard g(obs.device());
+  const int64_t B = obs.size(0), T = obs.size(1), E = obs.size(2);
+  TORCH_CHECK(noise.dim() == 4 && noise.size(0) == B && noise.size(2) == T && noise.size(3) == r &&
+                  noise.scalar_type() == at::kDouble,
+              "noise must be a (", B, ", S, ", T, ", ", r, ") float64 tensor");
+  const int64_t S = noise.size(1);
+  Tensor z = noise.stride(3) == 1 ? noise : noise.contiguous();
+  Tensor prm = params.contiguous();
+  TORCH_CHECK(prm.scalar_type() == at::kDouble && prm.dim() == 2 && prm.size(0) == B &&
+                  prm.size(1) == eks_param_len((int)n, (int)r),
+              "params must be a (", B, ", ", eks_param_len((int)n, (int)r), ") float64 tensor");
+  Tensor draws_tm = at::empty({T, B, S, n}, f64(obs));  // time-major: coalesced stores
+  Tensor latent = at::empty({B, S, T, r}, f64(obs));
+  Tensor out_tm = at::empty({T, B, n}, f64(obs));
+  Tensor status = at::empty({B}, i32(obs));
+  const size_t wsb = eks_draws_gaps_workspace_bytes(B, S, T, (int)n, (int)r);
+  Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 1)}, obs.options().dtype(at::kByte));
+  check(eks_draws_gaps(obs.data_ptr(), obs_dtype(obs), B, T, (int)E, (int)n, (int)r,
+                       obs.stride(0), obs.stride(1), obs.stride(2), obs.stride(3),
+                       mode_code(mode), prm.data_ptr<double>(), S, z.data_ptr<double>(),
+                       z.stride(0), z.stride(1), z.stride(2), 0, draws_tm.data_ptr<double>(),
+                       S * n, n, B * S * n, 1, latent.data_ptr<double>(),
+                       out_tm.data_ptr<double>(), n, B * n, 1, nullptr, ws.data_ptr(),
+                       (size_t)ws.numel(), status.data_ptr<int32_t>(), cur_stream(obs)),
+        "eks_draws_gaps");
+  return {draws_tm.permute({1, 2, 0, 3}).contiguous(), latent,
+          out_tm.permute({1, 0, 2}).contiguous(), status};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> draws_gaps_meta(const Tensor& obs, const Tensor&,
+                                                           const Tensor& noise, int64_t n,
+                                                           int64_t r, const std::string&) {
+  auto o = obs.options().dtype(at::kDouble);
+  return {at::empty({obs.size(0), noise.size(1), obs.size(1), n}, o),
+          at::empty({obs.size(0), noise.size(1), obs.size(1), r}, o),
+          at::empty({obs.size(0), obs.size(1), n}, o),
+          at::empty({obs.size(0)}, obs.options().dtype(at::kInt))};
+}
+// the noise a seeded eks_draws_gaps call generates, on `like`'s device: (B, S, T, r)
+Tensor draws_noise_gpu(const Tensor& like, int64_t B, int64_t S, int64_t T, int64_t r,
+                       int64_t seed) {
+  need_gpu(like, "like");
+  TORCH_CHECK(B >= 0 && S >= 0 && T >= 0, "B, S, T must be >= 0");
+  const c10::DeviceGuard g(like.device());
+  Tensor z = at::empty({B, S, T, r}, f64(like));
+  check(eks_draws_noise(B, S, T, (int)r, (uint64_t)seed, z.data_ptr<double>(), S * T * r, T * r,
+                        r, cur_stream(like)),
+        "eks_draws_noise");
+  return z;
+}
+Tensor draws_noise_meta(const Tensor& like, int64_t B, int64_t S, int64_t T, int64_t r, int64_t) {
+  return at::empty({B, S, T, r}, like.options().dtype(at::kDouble));
+}
 // the NLL of K candidate models per trajectory: params (K * B, P), row
 // k * B + b = candidate k of trajectory b -> nll (K, B), status (K, B)
 std::tuple<Tensor, Tensor> nll_sweep_gpu(const Tensor& obs, const Tensor& params, int64_t K,
@@ -604,6 +669,9 @@ TORCH_LIBRARY(eks, m) {
   m.def("smooth_var(Tensor obs, Tensor params, int n, int r) -> (Tensor, Tensor, Tensor)");
   m.def("smooth_gaps(Tensor obs, Tensor params, int n, int r, str mode) -> "
         "(Tensor out, Tensor var, Tensor nll, Tensor nobs, Tensor status)");
+  m.def("draws_gaps(Tensor obs, Tensor params, Tensor noise, int n, int r, str mode) -> "
+        "(Tensor draws, Tensor latent, Tensor out, Tensor status)");
+  m.def("draws_noise(Tensor like, int B, int S, int T, int r, int seed) -> Tensor");
   m.def("nll(Tensor obs, Tensor params, int n, int r, str mode, int flags) -> Tensor");
   m.def("nll_sweep(Tensor obs, Tensor params, int K, int n, int r, str mode) -> (Tensor, Tensor)");
   m.def("nll_sweep_gaps(Tensor obs, Tensor params, int K, int n, int r, str mode) -> "
@@ -627,6 +695,8 @@ TORCH_LIBRARY_IMPL(eks, CUDA, m) {
   m.impl("smooth", &smooth_gpu);
   m.impl("smooth_var", &smooth_var_gpu);
   m.impl("smooth_gaps", &smooth_gaps_gpu);
+  m.impl("draws_gaps", &draws_gaps_gpu);
+  m.impl("draws_noise", &draws_noise_gpu);
   m.impl("nll", &nll_gpu);
   m.impl("nll_sweep", &nll_sweep_gpu);
   m.impl("nll_sweep_gaps", &nll_sweep_gaps_gpu);
@@ -645,6 +715,8 @@ TORCH_LIBRARY_IMPL(eks, Meta, m) {
   m.impl("smooth", &smooth_meta);
   m.impl("smooth_var", &smooth_var_meta);
   m.impl("smooth_gaps", &smooth_gaps_meta);
+  m.impl("draws_gaps", &draws_gaps_meta);
+  m.impl("draws_noise", &draws_noise_meta);
   m.impl("nll", &nll_meta);
   m.impl("nll_sweep", &nll_sweep_meta);
   m.impl("nll_sweep_gaps", &nll_sweep_gaps_meta);

@@ -28,6 +28,10 @@ CPU tensor is a dispatch error).  Layout conventions are those of
     smooth_gaps (obs, params, n, r, mode) -> (out, var (B,T,n), nll (B), nobs (B), status):
                the smoother through missing observations (non-finite ensemble average
                or variance), its posterior variances and the NLL over the observed entries
+    draws_gaps (obs, params, noise (B,S,T,r), n, r, mode) -> (draws (B,S,T,n), latent (B,S,T,r),
+               out (B,T,n), status): joint draws from smooth_gaps's posterior (batch.draws_gaps;
+               the seeded form there).  draws_noise (like, B, S, T, r, seed) -> the noise
+               (B,S,T,r) a seeded call generates, on like's device
     ensemble_gaps (obs, mode, min_members) -> (yev bytes (EKS_YEV64 planes), nvalid (T,n,B) uint8):
                the ensemble over the finite members of each column, missing only where
                fewer than min_members are finite
@@ -45,7 +49,8 @@ from . import _lib
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libeks_torch.so")
 
-OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "smooth_gaps", "nll",
+OPS = ("ensemble", "forward", "backward", "smooth", "smooth_var", "smooth_gaps", "draws_gaps",
+       "draws_noise", "nll",
        "nll_sweep", "nll_sweep_gaps", "fit", "fit_gaps", "ensemble_gaps", "fit_pupil", "newton_filter",
        "interp1d")
 

@@ -73,6 +73,33 @@ def _run_gaps(yev, model: dict, mode: str = "median", want_var=False):
             T * n - int(res["nobs"][0].item()))
 
 
+def _posterior_draws(yev, params, *, n: int, r: int, S: int, seed: int, mode: str = "median",
+                     want_latent: bool = False):
+    """``S`` joint draws from the smoothing posterior of one keypoint, one
+    batch.draws_gaps call on the planes and packed model the smoother read ->
+    draws (S, T, n) and, if asked, the latent draws (S, T, r)."""
+    res = batch.draws_gaps(yev, params, n=n, r=r, S=int(S), seed=int(seed), mode=mode,
+                           want_latent=want_latent, want_out=False, check=True)
+    return (res["draws"][0].cpu().numpy(),
+            res["latent"][0].cpu().numpy() if want_latent else None)
+
+
+def _model_draws(yev, model: dict, S: int, seed: int, mode: str = "median"):
+    """_posterior_draws for a host model dict."""
+    params = batch.pack_params(model["m0"], model["S0"], model["A"], model["Q"], model["C"],
+                               model["offset"])
+    return _posterior_draws(yev, params, n=len(model["offset"]), r=len(model["m0"]), S=S,
+                            seed=seed, mode=mode)[0]
+
+
+# ``posterior_draws=S`` (default 0: nothing changes) with ``draws_seed``, in the
+# multi-camera, pupil and single-view wrappers below: the dict gains
+# 'posterior_draws', a float64 (S, T, n) array of S joint draws from the
+# smoothing posterior in the columns of the smoother's out (one extra
+# batch.draws_gaps call on the same planes and model).  Unlike the posterior
+# variances, the draws carry the correlation between frames.
+
+
 def _auto_smooth_param(yev, model: dict, mode: str = "median") -> float:
     """The smoothing parameter chosen by likelihood (batch.select_smooth_param)
     for one keypoint: ``model`` fitted with smooth_param = 1, ``yev`` the
@@ -100,7 +127,8 @@ def _check_min_members(min_members, allow_missing):
 
 def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, smooth_param,
                                        quantile_keep_pca, camera_names, posterior_var=False,
-                                       allow_missing=False, min_members=None):
+                                       allow_missing=False, min_members=None, posterior_draws=0,
+                                       draws_seed=0):
     """Multi-view PCA smoother for one keypoint (eks/multiview_pca_smoother.py:611-767).
 
     ``smooth_param=None``: chosen by minimising the filter's NLL on the device
@@ -158,6 +186,8 @@ def ensemble_kalman_smoother_multi_cam(markers_list_cameras, keypoint_ensemble, 
         dfs[cam + "_df"] = pd.DataFrame(arr, columns=pdindex)
     if posterior_var:
         dfs["posterior_var_df"] = _camera_dfs(pv[0], keypoint_ensemble, camera_names)
+    if posterior_draws:
+        dfs["posterior_draws"] = _model_draws(yev, model, posterior_draws, draws_seed)
     return dfs
 
 
@@ -219,8 +249,16 @@ def _pupil_dfs(out, ms, mx, my, keypoint_names, tracker_name, var=None, Vs=None)
     return res
 
 
+def _pupil_draws(res, yev, params, mx, my, S, seed):
+    """The pupil wrapper's draw keys: 'posterior_draws' (S, T, 8) in out's
+    columns and 'latents_posterior_draws' (S, T, 3) in latents_df's."""
+    draws, lat = _posterior_draws(yev, params, n=8, r=3, S=S, seed=seed, want_latent=True)
+    res['posterior_draws'] = draws
+    res['latents_posterior_draws'] = lat + np.array([0.0, mx, my])
+
+
 def _pupil_on_device(stack, keypoint_names, tracker_name, state_transition_matrix, pv,
-                     allow_missing, min_members):
+                     allow_missing, min_members, posterior_draws=0, draws_seed=0):
     """ensemble_kalman_smoother_pupil(fit_on_device=True): members -> fit ->
     smooth on the device; only the results come back."""
     A = np.asarray(state_transition_matrix, dtype=np.float64)
@@ -240,12 +278,15 @@ def _pupil_on_device(stack, keypoint_names, tracker_name, state_transition_matri
                      sm["Vs"][0].cpu().numpy() if pv else None)
     if allow_missing:
         res['n_missing'] = T * 8 - int(sm["nobs"][0].item())
+    if posterior_draws:
+        _pupil_draws(res, f["yev"], params, stats[1], stats[2], posterior_draws, draws_seed)
     return res
 
 
 def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
                                    state_transition_matrix, posterior_var=False,
-                                   allow_missing=False, min_members=None, fit_on_device=False):
+                                   allow_missing=False, min_members=None, fit_on_device=False,
+                                   posterior_draws=0, draws_seed=0):
     """IBL pupil smoother (eks/pupil_smoother.py:82-223).
 
     ``allow_missing=True``: a column whose ensemble average or variance is not
@@ -265,13 +306,19 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
     from batch.fit_pupil + batch.pupil_params instead of the host fit, and the
     smoother reads the planes the fit wrote (batch.smooth_gaps); the dict has
     the same keys.  Without ``allow_missing`` a frame the device fit finds
-    incomplete raises ValueError."""
+    incomplete raises ValueError.
+
+    ``posterior_draws=S``: also 'posterior_draws' (S, T, 8), joint posterior
+    draws in the columns of the smoother's out (fit.PUPIL_KEYS), and
+    'latents_posterior_draws' (S, T, 3) in the columns of latents_df, seeded
+    by ``draws_seed``."""
     _check_min_members(min_members, allow_missing)
     stack = np.stack([np.stack([np.asarray(df[k], dtype=np.float64) for k in fit.PUPIL_KEYS], 1)
                       for df in markers_list])  # (E, T, 8)
     if fit_on_device:
         return _pupil_on_device(stack, keypoint_names, tracker_name, state_transition_matrix,
-                                bool(posterior_var), allow_missing, min_members)
+                                bool(posterior_var), allow_missing, min_members,
+                                posterior_draws, draws_seed)
     yev, preds, ev = core.ensemble_handoff(stack, min_members=min_members)
     pv = bool(posterior_var)
     n_missing = None
@@ -286,6 +333,10 @@ def ensemble_kalman_smoother_pupil(markers_list, keypoint_names, tracker_name,
     res = _pupil_dfs(out, ms, model["mx"], model["my"], keypoint_names, tracker_name, var, Vs)
     if allow_missing:
         res['n_missing'] = n_missing
+    if posterior_draws:
+        params = batch.pack_params(model["m0"], model["S0"], model["A"], model["Q"], model["C"],
+                                   model["offset"])
+        _pupil_draws(res, yev, params, model["mx"], model["my"], posterior_draws, draws_seed)
     return res
 
 
@@ -367,7 +418,7 @@ def pupil_smoothing_sweep(markers_list, keypoint_names, tracker_name, diameter_s
 def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth_param,
                                          quantile_keep_pca=25, ensembling_mode="median",
                                          posterior_var=False, allow_missing=False,
-                                         min_members=None):
+                                         min_members=None, posterior_draws=0, draws_seed=0):
     """Single-view EKS for one keypoint (the reference
     snapshot has no single-view smoother).
 
@@ -421,6 +472,9 @@ def ensemble_kalman_smoother_single_view(markers_list, keypoint_ensemble, smooth
     if posterior_var:
         res['posterior_var_df'] = pd.DataFrame(np.stack([pv[0][:, 0], pv[0][:, 1], nan], 1),
                                                columns=idx)
+    if posterior_draws:
+        res['posterior_draws'] = _model_draws(yev, model, posterior_draws, draws_seed,
+                                              ensembling_mode)
     return res
 
 

@@ -360,6 +360,67 @@ int eks_smooth_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E,
                     size_t workspace_bytes, int32_t *status, void *stream);
 
 /*
+ * eks_draws_gaps -- S joint draws per trajectory from the smoothing posterior
+ * of eks_smooth_gaps (same inputs, missing rule, limits, error codes and
+ * status bits), by backward sampling on the device.  With J_t, D_t of the RTS
+ * pass (D_t = P_t - J_t S_t J_t^T), chol the lower Cholesky factor with
+ * positive diagonal and z(b,s,t,.) ~ N(0, I_r):
+ *     delta_{T-1} = chol(P_{T-1}) z_{T-1}
+ *     delta_t     = J_t delta_{t+1} + chol(D_t) z_t,   t = T-2 .. 0
+ *     x_t = ms_t + delta_t,   draws(b,s,t,j) = c_j x_t + offset_j
+ * time-parallel over the chunks of eks_smooth_gaps (the same chunk length,
+ * EKS_DBG_GAPS_CHUNK).  Consecutive frames of one draw are correlated as the
+ * posterior is (Cov(x_t, x_{t+1} | Y) = J_t Vs_{t+1}), which pvar cannot give.
+ *
+ *   S        draws per trajectory.  B = 0 or S = 0: EKS_OK, nothing of the draw
+ *            stage is launched and draws is untouched; S < 0: EKS_ERR_ARG.
+ *   noise    z(b,s,t,i) = noise[b*zb + s*zs + t*zt + i] (f64, i contiguous), or
+ *            NULL: the kernels generate z from `seed` (below) and no noise
+ *            tensor is allocated or read
+ *   draws    draws(b,s,t,j) = draws[b*db + s*ds + t*dt + j*dj] (f64); REQUIRED
+ *   xdraws   (B, S, T, r) contiguous latent draws x_t, or NULL
+ *   out, pvar  eks_smooth_gaps's, with the same values; both optional here
+ *            (pvar has out's strides, so it needs out: else EKS_ERR_ARG)
+ *   status   (B) int32, REQUIRED; zeroed by the call.  eks_smooth_gaps's bits,
+ *            and EKS_STATUS_SINGULAR for a trajectory where a Cholesky pivot of
+ *            D_t (or P_{T-1}) is not > 0 (a NaN pivot included): ALL draws of
+ *            that trajectory are NaN, other trajectories are unaffected.
+ * r = 2 or 3, n <= 64, E <= eks_max_members(), B * S <= 2^28, T <= 2^40, else
+ * EKS_ERR_UNSUPPORTED (the size query returns 0).  Results are bit-reproducible
+ * from call to call, and draw (b, s) has the same bits whatever S is and
+ * whichever other draws are asked for; its noise z(b,s,.,.) does not depend on
+ * B, S, the chunk length or the launch shape.
+ *
+ * Seeded noise (noise == NULL), also written out by eks_draws_noise: component
+ * i of z(b,s,t,.) comes from block i / 2 of a counter-based generator,
+ * Philox4x32-10 (Salmon et al., SC 2011; multipliers 0xD2511F53, 0xCD9E8D57,
+ * key increments 0x9E3779B9, 0xBB67AE85):
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (t & 0xffffffff, (t >> 32) | (block << 8), s, b)
+ *     (x0, x1, x2, x3) = philox4x32_10(counter, key)
+ *     k1 = (x0 << 21) | (x1 >> 11),  k2 = (x2 << 21) | (x3 >> 11)   (53 bits each)
+ *     u1 = (k1 + 1) * 2^-53 in (0, 1],  u2 = k2 * 2^-53 in [0, 1)
+ *     z[2 block]     = sqrt(-2 log u1) * cos(6.283185307179586 * u2)
+ *     z[2 block + 1] = sqrt(-2 log u1) * sin(6.283185307179586 * u2)
+ * (r = 3 drops the second value of block 1).  eks_draws_noise writes
+ * z(b,s,t,i) to noise[b*zb + s*zs + t*zt + i] with the same device function,
+ * so eks_draws_gaps(seed) and eks_draws_gaps(noise = eks_draws_noise(seed))
+ * agree; under EKS_DBG_DRAWS_RAW it writes (double)k1, (double)k2 instead.
+ */
+size_t eks_draws_gaps_workspace_bytes(int64_t B, int64_t S, int64_t T, int n, int r);
+int64_t eks_draws_gaps_chunk_len(int64_t B, int64_t T, int r);
+int eks_draws_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, int n, int r,
+                   int64_t sb, int64_t st, int64_t se, int64_t sj, int mode, const double *params,
+                   int64_t S, const double *noise, int64_t zb, int64_t zs, int64_t zt,
+                   uint64_t seed /* used iff noise == NULL */,
+                   double *draws, int64_t db, int64_t ds, int64_t dt, int64_t dj, /* REQUIRED */
+                   double *xdraws /* (B,S,T,r) or NULL */,
+                   double *out, int64_t ob, int64_t ot, int64_t oj, double *pvar, /* or NULL */
+                   void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+int eks_draws_noise(int64_t B, int64_t S, int64_t T, int r, uint64_t seed, double *noise,
+                    int64_t zb, int64_t zs, int64_t zt, void *stream);
+
+/*
  * eks_nll_sweep_gaps -- eks_nll_sweep through missing observations: the
  * Gaussian innovation NLL over the OBSERVED entries (eks_smooth_gaps's nll and
  * its missing rule: column (t, j) is missing iff its ensemble average or
@@ -663,10 +724,14 @@ int eks_interp1d(const double *x, int64_t nx, const double *y, int64_t ncol, int
  *   EKS_DBG_GAPS_SWEEP_CHUNK  eks_nll_sweep_gaps's chunk length, with the same
  *                          rule.  Set it before
  *                          eks_nll_sweep_gaps_workspace_bytes.
+ *   EKS_DBG_DRAWS_RAW      non-zero: eks_draws_noise writes the generator's
+ *                          53-bit integers (k1, k2 of each block, as doubles)
+ *                          in place of the normals.  eks_draws_gaps ignores it.
  */
 enum { EKS_DBG_WAIT_US = 1, EKS_DBG_A3_SLICE_BYTES = 2, EKS_DBG_FIT_SELECT = 3,
        EKS_DBG_A3_MODE = 4, EKS_DBG_A3_LB = 5, EKS_DBG_RT_FORM = 6, EKS_DBG_PVAR_CHUNK = 7,
-       EKS_DBG_SWEEP_CHUNK = 8, EKS_DBG_GAPS_CHUNK = 9, EKS_DBG_GAPS_SWEEP_CHUNK = 10 };
+       EKS_DBG_SWEEP_CHUNK = 8, EKS_DBG_GAPS_CHUNK = 9, EKS_DBG_GAPS_SWEEP_CHUNK = 10,
+       EKS_DBG_DRAWS_RAW = 11 };
 int64_t eks_debug_set(int key, int64_t value);
 
 /*
