@@ -14,6 +14,8 @@ copied to the host; everything is stream-ordered on the current stream.
 """
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 
 from . import _lib
@@ -32,6 +34,25 @@ class Yev:
         self.buf, self.B, self.T, self.E, self.n, self.code, self.mode = buf, B, T, E, n, code, mode
         self.shape = (B, T, E, n)
         self.device = buf.device
+
+    @staticmethod
+    def layout(B: int, T: int, n: int, code: int):
+        """(bytes of the y planes, byte offset of the ev planes, bytes in all)
+        of the planes of B trajectories: T * n planes of B values of y (float32
+        for EKS_YEV32, else float64), then from the next 256-byte boundary as
+        many of ev (float64) -- include/eks_hip.h eks_yev_bytes."""
+        ybytes = T * n * B * (4 if code == _lib.EKS_YEV32 else 8)
+        ev_off = (ybytes + 255) // 256 * 256
+        return ybytes, ev_off, ev_off + T * n * B * 8
+
+    def planes(self):
+        """The y and ev planes as (T, n, B) views of ``buf``."""
+        import torch
+        ybytes, ev_off, end = Yev.layout(self.B, self.T, self.n, self.code)
+        ydt = torch.float32 if self.code == _lib.EKS_YEV32 else torch.float64
+        shape = (self.T, self.n, self.B)
+        return (self.buf[:ybytes].view(ydt).reshape(shape),
+                self.buf[ev_off:end].view(torch.float64).reshape(shape))
 
 
 def param_len(n: int, r: int) -> int:
@@ -104,21 +125,95 @@ def model_flags(A, C, Q=None) -> int:
     return f
 
 
-def _obs_code(obs, n: int):
-    """(B, T, E, input code) of a member view or a Yev hand-off."""
+_FIT_KINDS = {"singleview": _lib.EKS_FIT_SINGLEVIEW, "multicam": _lib.EKS_FIT_MULTICAM}
+
+
+def _mode_code(mode: str) -> int:
+    if mode not in ("median", "mean"):
+        raise ValueError(f"{mode} averaging not supported")
+    return _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
+
+
+# what an entry point passes for its input: eks_x(ptr, code, B, T, E, n, [r,] *strides, mode, ..)
+_MemberIn = collections.namedtuple("_MemberIn", "ptr code B T E strides mode")
+
+
+def _member_input(obs, n: int, mode, members_only: bool = False):
+    """The input arguments of an entry point for a (B, T, E, n) member view of
+    any strides or, unless ``members_only``, a ``Yev`` made in ``mode``: the
+    pointer, the input code, B, T, E, the four strides (0 for planes) and the
+    code of ``mode`` (None, unchecked, for an entry point without one).
+    ``ptr`` is a bare address: the caller keeps ``obs`` (a temporary such as
+    ``obs[rows]`` too) alive until the call that reads it has been launched.
+    Needs no device: the checks are the same for CPU tensors."""
     import torch
-    if not isinstance(obs, Yev) and obs.dim() != 4:
+    yev = isinstance(obs, Yev)
+    if yev and members_only:
+        raise TypeError("obs must be a member view: this entry point reads no hand-off planes")
+    if not yev and obs.dim() != 4:
         raise ValueError("obs must be viewed as (B, T, E, n)")
     B, T, E, nn = obs.shape
     if nn != n:
         raise ValueError(f"obs has {nn} coordinates, expected n={n}")
-    if isinstance(obs, Yev):
-        return B, T, E, obs.code
-    if obs.dtype == torch.float32:
-        return B, T, E, _lib.EKS_F32
-    if obs.dtype == torch.float64:
-        return B, T, E, _lib.EKS_F64
-    raise TypeError("obs must be float32 or float64")
+    m = None if mode is None else _mode_code(mode)
+    if yev:
+        if mode is not None and mode != obs.mode:
+            raise ValueError("the hand-off planes were made in another averaging mode")
+        return _MemberIn(obs.buf.data_ptr(), obs.code, B, T, E, (0, 0, 0, 0), m)
+    if obs.dtype not in (torch.float32, torch.float64):
+        raise TypeError("obs must be float32 or float64")
+    code = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
+    return _MemberIn(obs.data_ptr(), code, B, T, E, tuple(obs.stride()), m)
+
+
+def _check_params(params, rows: int, n: int, r: int, ok: bool = True):
+    """``params`` holds ``rows`` packed models: B, or (``ok``: K >= 0) K * B candidates."""
+    import torch
+    P = param_len(n, r)
+    if not ok or params.shape != (rows, P) or params.dtype != torch.float64 \
+            or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous ({rows}, {P}) float64 tensor")
+
+
+def _status_words(status, shape: tuple, dev):
+    """The caller's status tensor if it has the entry point's form, a new one if None."""
+    import torch
+    if status is None:
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+    if tuple(status.shape) != shape or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError(f"status must be a contiguous {shape} int32 tensor")
+    return status
+
+
+def _yev_out(keep_yev, shape: tuple, code: int, mode: str, nbytes: int, dev):
+    """The ``Yev`` an entry point writes its planes to: the buffer of
+    ``keep_yev`` when that is a Yev large enough, else a new one; a Yev of
+    another shape, code or mode gets a new header on its buffer."""
+    import torch
+    if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
+        if (keep_yev.shape, keep_yev.code, keep_yev.mode) == (shape, code, mode):
+            return keep_yev
+        return Yev(keep_yev.buf, *shape, code, mode)
+    return Yev(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), *shape, code, mode)
+
+
+def _raise_on_status(status, fn: str, errors: int) -> int:
+    """Synchronises and raises on the bits of ``status`` that ``errors`` names:
+    ValueError on EKS_STATUS_BAD_MODEL (a sweep's candidates) and on
+    EKS_STATUS_SCAN (``fn`` has no path for an exact observation), LinAlgError
+    on EKS_STATUS_SINGULAR.  Returns the bits that are set."""
+    bits = status_bits(status)
+    if bits & errors & _lib.EKS_STATUS_BAD_MODEL:
+        raise ValueError("the candidates of a trajectory must share C and offset")
+    if bits & errors & _lib.EKS_STATUS_SCAN:
+        raise ValueError(f"an observed column with zero ensemble variance: {fn} does not serve it")
+    if bits & errors & _lib.EKS_STATUS_SINGULAR:
+        raise np.linalg.LinAlgError("Singular matrix")
+    return bits
+
+
+def _ptr(x):
+    return x.data_ptr() if x is not None else None
 
 
 def smooth_var(obs, params, *, n: int, r: int, want_Vs: bool = False, status=None, stream=None):
@@ -131,25 +226,19 @@ def smooth_var(obs, params, *, n: int, r: int, want_Vs: bool = False, status=Non
     EKS_STATUS_SCAN and NaN; ``smooth(..., want_var=True, check=True)``
     recomputes those."""
     torch = _lib.require_gpu()
-    B, T, E, dt = _obs_code(obs, n)
-    if params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    i = _member_input(obs, n, None)
+    B, T = i.B, i.T
+    _check_params(params, B, n, r)
     dev = obs.device
     var = torch.empty((T, B, n), dtype=torch.float64, device=dev).permute(1, 0, 2)
     Vs = torch.empty((B, T, r, r), dtype=torch.float64, device=dev) if want_Vs else None
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = _status_words(status, (B,), dev)
     lib = _lib.load()
     ws = workspace(lib.eks_smooth_var_workspace_bytes(B, T, n, r), dev, slot="smooth_var")
-    yev = isinstance(obs, Yev)
-    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
-    vb, vt, vj = var.stride()
     _lib.check(lib.eks_smooth_var(
-        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
-        params.data_ptr(), var.data_ptr(), vb, vt, vj,
-        Vs.data_ptr() if Vs is not None else None, ws.data_ptr(), ws.numel(),
-        status.data_ptr(), _lib.stream_ptr(stream)), "eks_smooth_var")
+        i.ptr, i.code, B, T, i.E, n, r, *i.strides, params.data_ptr(), var.data_ptr(),
+        *var.stride(), _ptr(Vs), ws.data_ptr(), ws.numel(), status.data_ptr(),
+        _lib.stream_ptr(stream)), "eks_smooth_var")
     return dict(var=var, Vs=Vs, status=status)
 
 
@@ -159,23 +248,19 @@ def _var_unfused(obs, params, rows, *, n: int, r: int, mode: str):
     a projection: the path for exact observations, which have no W_t."""
     import torch
     lib = _lib.load()
-    B, T, E, dt = _obs_code(obs, n)
     dev = obs.device
     k = int(rows.numel())
+    T = obs.shape[1]
     f64 = dict(dtype=torch.float64, device=dev)
     if isinstance(obs, Yev):
-        ysize = 4 if obs.code == _lib.EKS_YEV32 else 8
-        off = (T * n * B * ysize + 255) // 256 * 256
-        planes = obs.buf[off:off + T * n * B * 8].view(torch.float64).reshape(T, n, B)
-        ev = planes[:, :, rows].permute(2, 0, 1).contiguous()
+        ev = obs.planes()[1][:, :, rows].permute(2, 0, 1).contiguous()
         y = torch.zeros_like(ev)  # the covariances do not depend on y
     else:
-        sub = obs[rows]
+        sub = obs[rows]  # a gathered copy: it must outlive the launch that reads i.ptr
+        i = _member_input(sub, n, mode)
         y = torch.empty((k, T, n), **f64)
         ev = torch.empty((k, T, n), **f64)
-        sb, st, se, sj = sub.stride()
-        _lib.check(lib.eks_ensemble(sub.data_ptr(), dt, k, T, E, n, sb, st, se, sj,
-                                    _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN,
+        _lib.check(lib.eks_ensemble(i.ptr, i.code, k, T, i.E, n, *i.strides, i.mode,
                                     y.data_ptr(), ev.data_ptr(), _lib.stream_ptr()), "eks_ensemble")
     p = params[rows]
     rr = r * r
@@ -225,30 +310,9 @@ def smooth(obs, params, *, n: int, r: int, mode: str = "median", out=None, want_
     sequential algorithm if the time-parallel scan reported a breakdown.
     """
     torch = _lib.require_gpu()
-    if isinstance(obs, Yev):
-        B, T, E, nn = obs.shape
-        if nn != n:
-            raise ValueError(f"obs has {nn} coordinates, expected n={n}")
-        if mode != obs.mode:
-            raise ValueError("the hand-off planes were made in another averaging mode")
-        dt = obs.code
-    else:
-        if obs.dim() != 4:
-            raise ValueError("obs must be viewed as (B, T, E, n)")
-        B, T, E, nn = obs.shape
-        if nn != n:
-            raise ValueError(f"obs has {nn} coordinates, expected n={n}")
-        if obs.dtype == torch.float32:
-            dt = _lib.EKS_F32
-        elif obs.dtype == torch.float64:
-            dt = _lib.EKS_F64
-        else:
-            raise TypeError("obs must be float32 or float64")
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
-    if params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    i = _member_input(obs, n, mode)
+    B, T = i.B, i.T
+    _check_params(params, B, n, r)
     dev = obs.device
     if not want_out:  # filter only: NLL per trajectory, no backward pass
         want_nll, want_ms, out = True, False, None
@@ -256,20 +320,14 @@ def smooth(obs, params, *, n: int, r: int, mode: str = "median", out=None, want_
         out = torch.empty((T, B, n), dtype=torch.float64, device=dev).permute(1, 0, 2)
     ms = torch.empty((B, T, r), dtype=torch.float64, device=dev) if want_ms else None
     nll = torch.empty((B,), dtype=torch.float64, device=dev) if want_nll else None
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = _status_words(status, (B,), dev)
     lib = _lib.load()
-    nbytes = lib.eks_smooth_workspace_bytes(B, T, n, r, E, algo)
-    ws = workspace(nbytes, dev)
-    sb, st, se, sj = (0, 0, 0, 0) if isinstance(obs, Yev) else obs.stride()
+    ws = workspace(lib.eks_smooth_workspace_bytes(B, T, n, r, i.E, algo), dev)
     ob, ot, oj = out.stride() if out is not None else (0, 0, 0)
     _lib.check(lib.eks_smooth(
-        obs.buf.data_ptr() if isinstance(obs, Yev) else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
-        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(),
-        out.data_ptr() if out is not None else None, ob, ot, oj,
-        ms.data_ptr() if ms is not None else None,
-        nll.data_ptr() if nll is not None else None, ws.data_ptr(), ws.numel(), flags, algo,
-        status.data_ptr(), _lib.stream_ptr(stream)), "eks_smooth")
+        i.ptr, i.code, B, T, i.E, n, r, *i.strides, i.mode, params.data_ptr(), _ptr(out), ob, ot,
+        oj, _ptr(ms), _ptr(nll), ws.data_ptr(), ws.numel(), flags, algo, status.data_ptr(),
+        _lib.stream_ptr(stream)), "eks_smooth")
     res = dict(out=out, ms=ms, nll=nll, status=status, var=None, Vs=None)
     pv = None
     if want_var or want_Vs:  # the variance pass: own workspace slot, own status until checked
@@ -310,36 +368,22 @@ def fit(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_keep: f
     kind "singleview" (r == n) or "multicam" (PCA with r
     axes; eks/multiview_pca_smoother.py:684-731)."""
     torch = _lib.require_gpu()
-    if obs.dim() != 4 or obs.shape[3] != n:
-        raise ValueError("obs must be viewed as (B, T, E, n)")
-    B, T, E, _ = obs.shape
-    dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
-    if obs.dtype not in (torch.float32, torch.float64):
-        raise TypeError("obs must be float32 or float64")
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
-    k = {"singleview": _lib.EKS_FIT_SINGLEVIEW, "multicam": _lib.EKS_FIT_MULTICAM}[kind]
+    i = _member_input(obs, n, mode, members_only=True)
+    B, T, E = i.B, i.T, i.E
+    k = _FIT_KINDS[kind]
     lib = _lib.load()
     if params is None:
         params = torch.empty((B, param_len(n, r)), dtype=torch.float64, device=obs.device)
-    elif params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=obs.device)
+    else:
+        _check_params(params, B, n, r)
+    status = _status_words(status, (B,), obs.device)
     ws = workspace(lib.eks_fit_workspace_bytes(B, T, n), obs.device, slot="fit")
-    sb, st, se, sj = obs.stride()
-    m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
     yev = None
     if keep_yev:
         # a Yev object (reused when passed in) receives the ensemble planes
-        nbytes = lib.eks_yev_bytes(B, T, n, dt, E, m)
-        if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
-            yev = keep_yev
-        else:
-            yev = Yev(torch.empty(nbytes, dtype=torch.uint8, device=obs.device), B, T, E, n,
-                      lib.eks_yev_dtype(dt, E, m), mode)
-    _lib.check(lib.eks_fit(obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj, m, k,
+        yev = _yev_out(keep_yev, (B, T, E, n), lib.eks_yev_dtype(i.code, E, i.mode), mode,
+                       lib.eks_yev_bytes(B, T, n, i.code, E, i.mode), obs.device)
+    _lib.check(lib.eks_fit(i.ptr, i.code, B, T, E, n, r, *i.strides, i.mode, k,
                            float(smooth_param), float(quantile_keep), params.data_ptr(),
                            ws.data_ptr(), ws.numel(), status.data_ptr(),
                            yev.buf.data_ptr() if yev is not None else None, _lib.stream_ptr()),
@@ -379,62 +423,31 @@ def fit_gaps(obs, *, kind: str, n: int, r: int, smooth_param: float, quantile_ke
         if keep_yev is not None:
             raise ValueError("keep_yev cannot be combined with a Yev input: the planes are read, "
                              "not written")
-        if obs.n != n:
-            raise ValueError(f"obs has {obs.n} coordinates, expected n={n}")
-        B, T, E = obs.B, obs.T, obs.E
-        dt = obs.code
         mode = obs.mode
-    else:
-        if obs.dim() != 4 or obs.shape[3] != n:
-            raise ValueError("obs must be viewed as (B, T, E, n)")
-        B, T, E, _ = obs.shape
-        if obs.dtype not in (torch.float32, torch.float64):
-            raise TypeError("obs must be float32 or float64")
-        dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
-    k = {"singleview": _lib.EKS_FIT_SINGLEVIEW, "multicam": _lib.EKS_FIT_MULTICAM}[kind]
+    i = _member_input(obs, n, mode)
+    B, T, E = i.B, i.T, i.E
+    k = _FIT_KINDS[kind]
     lib = _lib.load()
     dev = obs.device
     if params is None:
         params = torch.empty((B, param_len(n, r)), dtype=torch.float64, device=dev)
-    elif params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-    elif status.shape != (B,) or status.dtype != torch.int32 or not status.is_contiguous():
-        raise ValueError(f"status must be a contiguous ({B},) int32 tensor")
+    else:
+        _check_params(params, B, n, r)
+    status = _status_words(status, (B,), dev)
     ncomplete = torch.empty((B,), dtype=torch.int32, device=dev)
     nkept = torch.empty((B,), dtype=torch.int32, device=dev)
     ws = workspace(lib.eks_fit_gaps_workspace_bytes(B, T, n), dev, slot="fit_gaps")
-    m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
-    if from_yev:
-        _lib.check(lib.eks_fit_gaps(obs.buf.data_ptr(), dt, B, T, E, n, r, 0, 0, 0, 0, m, k,
-                                    float(smooth_param), float(quantile_keep), params.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), status.data_ptr(), None,
-                                    ncomplete.data_ptr(), nkept.data_ptr(), _lib.stream_ptr()),
-                   "eks_fit_gaps")
-        return _fit_gaps_result(check, B, params, status, obs, ncomplete, nkept)
-    sb, st, se, sj = obs.stride()
-    nbytes = lib.eks_yev_bytes(B, T, n, dt, E, m)
-    code = lib.eks_yev_dtype(dt, E, m)
-    if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
-        yev = keep_yev  # the buffer is reused; a Yev of another shape gets a new header
-        if (yev.shape, yev.code, yev.mode) != ((B, T, E, n), code, mode):
-            yev = Yev(keep_yev.buf, B, T, E, n, code, mode)
+    if from_yev:  # the planes are read: none are written
+        yev, yptr = obs, None
     else:
-        yev = Yev(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), B, T, E, n, code,
-                  mode)
-    _lib.check(lib.eks_fit_gaps(obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj, m, k,
+        yev = _yev_out(keep_yev, (B, T, E, n), lib.eks_yev_dtype(i.code, E, i.mode), mode,
+                       lib.eks_yev_bytes(B, T, n, i.code, E, i.mode), dev)
+        yptr = yev.buf.data_ptr()
+    _lib.check(lib.eks_fit_gaps(i.ptr, i.code, B, T, E, n, r, *i.strides, i.mode, k,
                                 float(smooth_param), float(quantile_keep), params.data_ptr(),
-                                ws.data_ptr(), ws.numel(), status.data_ptr(), yev.buf.data_ptr(),
+                                ws.data_ptr(), ws.numel(), status.data_ptr(), yptr,
                                 ncomplete.data_ptr(), nkept.data_ptr(), _lib.stream_ptr()),
                "eks_fit_gaps")
-    return _fit_gaps_result(check, B, params, status, yev, ncomplete, nkept)
-
-
-def _fit_gaps_result(check, B, params, status, yev, ncomplete, nkept):
     if check and B > 0:
         bad = int((ncomplete == 0).sum().item())
         if bad:
@@ -459,31 +472,18 @@ def ensemble_gaps(obs, *, n: int, mode: str = "median", min_members: int,
     member has ev = 0, an exact observation to ``smooth_gaps``
     (EKS_STATUS_SCAN): use ``min_members >= 2``."""
     torch = _lib.require_gpu()
-    if obs.dim() != 4 or obs.shape[3] != n:
-        raise ValueError("obs must be viewed as (B, T, E, n)")
-    B, T, E, _ = obs.shape
-    if obs.dtype not in (torch.float32, torch.float64):
-        raise TypeError("obs must be float32 or float64")
-    dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
+    i = _member_input(obs, n, mode, members_only=True)
+    B, T, E = i.B, i.T, i.E
     min_members = int(min_members)
     if not 1 <= min_members <= E:
         raise ValueError(f"min_members={min_members} outside 1..E={E}")
     lib = _lib.load()
     dev = obs.device
-    m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
-    nbytes = lib.eks_yev_bytes(B, T, n, _lib.EKS_F64, E, m)
-    if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
-        yev = Yev(keep_yev.buf, B, T, E, n, _lib.EKS_YEV64, mode)
-    else:
-        yev = Yev(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), B, T, E, n,
-                  _lib.EKS_YEV64, mode)
+    yev = _yev_out(keep_yev, (B, T, E, n), _lib.EKS_YEV64, mode,
+                   lib.eks_yev_bytes(B, T, n, _lib.EKS_F64, E, i.mode), dev)
     nvalid = torch.empty((T, n, B), dtype=torch.uint8, device=dev) if want_nvalid else None
-    sb, st, se, sj = obs.stride()
-    _lib.check(lib.eks_ensemble_gaps(obs.data_ptr(), dt, B, T, E, n, sb, st, se, sj, m,
-                                     min_members, yev.buf.data_ptr(),
-                                     nvalid.data_ptr() if nvalid is not None and B > 0 else None,
+    _lib.check(lib.eks_ensemble_gaps(i.ptr, i.code, B, T, E, n, *i.strides, i.mode, min_members,
+                                     yev.buf.data_ptr(), _ptr(nvalid) if B > 0 else None,
                                      _lib.stream_ptr()),
                "eks_ensemble_gaps")
     return dict(yev=yev, nvalid=nvalid)
@@ -520,43 +520,22 @@ def fit_pupil(obs, *, mode: str = "median", check: bool = True, keep_yev=None):
         if keep_yev is not None:
             raise ValueError("keep_yev cannot be combined with a Yev input: the planes are read, "
                              "not written")
-        if obs.n != n:
-            raise ValueError(f"obs has {obs.n} coordinates, the pupil model has {n}")
-        B, T, E = obs.B, obs.T, obs.E
-        dt = obs.code
         mode = obs.mode
-    else:
-        if obs.dim() != 4 or obs.shape[3] != n:
-            raise ValueError("obs must be viewed as (B, T, E, 8)")
-        B, T, E, _ = obs.shape
-        if obs.dtype not in (torch.float32, torch.float64):
-            raise TypeError("obs must be float32 or float64")
-        dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
+    i = _member_input(obs, n, mode)
+    B, T, E = i.B, i.T, i.E
     lib = _lib.load()
     dev = obs.device
-    m = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
     stats = torch.empty((B, 6), dtype=torch.float64, device=dev)
     ncomplete = torch.empty((B,), dtype=torch.int32, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
     ws = workspace(lib.eks_fit_pupil_workspace_bytes(B, T), dev, slot="fit_pupil")
-    if from_yev:
-        yev = obs
-        src, strides, yptr = obs.buf.data_ptr(), (0, 0, 0, 0), None
-    else:
-        yev = None
-        if keep_yev is not None and keep_yev is not False:
-            nbytes = lib.eks_yev_bytes(B, T, n, _lib.EKS_F64, E, m)
-            if isinstance(keep_yev, Yev) and keep_yev.buf.numel() >= nbytes:
-                yev = Yev(keep_yev.buf, B, T, E, n, _lib.EKS_YEV64, mode)
-            else:
-                yev = Yev(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), B, T, E, n,
-                          _lib.EKS_YEV64, mode)
-        src, strides = obs.data_ptr(), obs.stride()
-        yptr = yev.buf.data_ptr() if yev is not None else None
+    yev = obs if from_yev else None  # the planes are read: none are written
+    if not from_yev and keep_yev is not None and keep_yev is not False:
+        yev = _yev_out(keep_yev, (B, T, E, n), _lib.EKS_YEV64, mode,
+                       lib.eks_yev_bytes(B, T, n, _lib.EKS_F64, E, i.mode), dev)
+    yptr = None if from_yev or yev is None else yev.buf.data_ptr()
     if B > 0:
-        _lib.check(lib.eks_fit_pupil(src, dt, B, T, E, n, *strides, m, stats.data_ptr(),
+        _lib.check(lib.eks_fit_pupil(i.ptr, i.code, B, T, E, n, *i.strides, i.mode, stats.data_ptr(),
                                      ncomplete.data_ptr(), ws.data_ptr(), ws.numel(),
                                      status.data_ptr(), yptr, _lib.stream_ptr()),
                    "eks_fit_pupil")
@@ -670,17 +649,14 @@ def nll(obs, params, *, n: int, r: int, mode: str = "median", flags: int = 0, al
 def _yev_rows(obs: Yev, rows):
     """The hand-off planes of the trajectories ``rows`` as a Yev of their own."""
     import torch
-    B, T, E, n = obs.shape
-    ysize, ydt = (4, torch.float32) if obs.code == _lib.EKS_YEV32 else (8, torch.float64)
-    off = (T * n * B * ysize + 255) // 256 * 256
-    y = obs.buf[:T * n * B * ysize].view(ydt).reshape(T * n, B)[:, rows].contiguous()
-    ev = obs.buf[off:off + T * n * B * 8].view(torch.float64).reshape(T * n, B)[:, rows].contiguous()
+    _, T, E, n = obs.shape
     k = int(rows.numel())
-    off2 = (T * n * k * ysize + 255) // 256 * 256
-    buf = torch.zeros(off2 + T * n * k * 8, dtype=torch.uint8, device=obs.device)
-    buf[:T * n * k * ysize] = y.view(torch.uint8).flatten()
-    buf[off2:] = ev.view(torch.uint8).flatten()
-    return Yev(buf, k, T, E, n, obs.code, obs.mode)
+    nbytes = Yev.layout(k, T, n, obs.code)[2]
+    sub = Yev(torch.zeros(nbytes, dtype=torch.uint8, device=obs.device), k, T, E, n, obs.code,
+              obs.mode)
+    for dst, src in zip(sub.planes(), obs.planes()):
+        dst.copy_(src[:, :, rows])
+    return sub
 
 
 def nll_sweep(obs, params, *, K: int, n: int, r: int, mode: str = "median", check: bool = True,
@@ -700,44 +676,28 @@ def nll_sweep(obs, params, *, K: int, n: int, r: int, mode: str = "median", chec
     offset differ between candidates) raises ValueError, EKS_STATUS_SINGULAR
     LinAlgError."""
     torch = _lib.require_gpu()
-    B, T, E, dt = _obs_code(obs, n)
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
-    yev = isinstance(obs, Yev)
-    if yev and mode != obs.mode:
-        raise ValueError("the hand-off planes were made in another averaging mode")
-    P = param_len(n, r)
-    if K < 0 or params.shape != (K * B, P) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({K * B}, {P}) float64 tensor")
+    i = _member_input(obs, n, mode)
+    B, T = i.B, i.T
+    _check_params(params, K * B, n, r, ok=K >= 0)
     dev = obs.device
     out = torch.empty((K, B), dtype=torch.float64, device=dev)
-    if status is None:
-        status = torch.empty((K, B), dtype=torch.int32, device=dev)
-    elif status.shape != (K, B) or status.dtype != torch.int32 or not status.is_contiguous():
-        raise ValueError(f"status must be a contiguous ({K}, {B}) int32 tensor")
+    status = _status_words(status, (K, B), dev)
     lib = _lib.load()
     ws = workspace(lib.eks_nll_sweep_workspace_bytes(B, K, T, n, r), dev, slot="nll_sweep")
-    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
     _lib.check(lib.eks_nll_sweep(
-        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
-        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(), K,
-        out.data_ptr(), ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)),
-        "eks_nll_sweep")
+        i.ptr, i.code, B, T, i.E, n, r, *i.strides, i.mode, params.data_ptr(), K, out.data_ptr(),
+        ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)), "eks_nll_sweep")
     if check and K * B > 0:
-        bits = status_bits(status)
-        if bits & _lib.EKS_STATUS_BAD_MODEL:
-            raise ValueError("the candidates of a trajectory must share C and offset")
+        bits = _raise_on_status(status, "eks_nll_sweep", _lib.EKS_STATUS_BAD_MODEL)
         if bits & _lib.EKS_STATUS_SCAN:
             rows = torch.nonzero(((status & _lib.EKS_STATUS_SCAN) != 0).any(dim=0)).flatten()
-            sub = _yev_rows(obs, rows) if yev else obs[rows]
-            cand = params.view(K, B, P)
+            sub = _yev_rows(obs, rows) if isinstance(obs, Yev) else obs[rows]
+            cand = params.view(K, B, -1)
             for k in range(K):
                 out[k, rows] = nll(sub, cand[k, rows].contiguous(), n=n, r=r, mode=mode,
                                    check=True)
             status[:, rows] &= ~_lib.EKS_STATUS_SCAN
-        if status_bits(status) & _lib.EKS_STATUS_SINGULAR:
-            raise np.linalg.LinAlgError("Singular matrix")
+        _raise_on_status(status, "eks_nll_sweep", _lib.EKS_STATUS_SINGULAR)
     return out
 
 
@@ -758,15 +718,9 @@ def smooth_gaps(obs, params, *, n: int, r: int, mode: str = "median", want_var: 
     LinAlgError on EKS_STATUS_SINGULAR and ValueError on EKS_STATUS_SCAN (an
     observed column with zero ensemble variance); there is no fallback path."""
     torch = _lib.require_gpu()
-    B, T, E, dt = _obs_code(obs, n)
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
-    yev = isinstance(obs, Yev)
-    if yev and mode != obs.mode:
-        raise ValueError("the hand-off planes were made in another averaging mode")
-    if params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    i = _member_input(obs, n, mode)
+    B, T = i.B, i.T
+    _check_params(params, B, n, r)
     dev = obs.device
     f64 = dict(dtype=torch.float64, device=dev)
     out = torch.empty((T, B, n), **f64).permute(1, 0, 2)
@@ -775,28 +729,16 @@ def smooth_gaps(obs, params, *, n: int, r: int, mode: str = "median", want_var: 
     ms = torch.empty((B, T, r), **f64) if want_ms else None
     nll_ = torch.empty((B,), **f64) if want_nll else None
     nobs = torch.empty((B,), dtype=torch.int32, device=dev)
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = _status_words(status, (B,), dev)
     lib = _lib.load()
     ws = workspace(lib.eks_smooth_gaps_workspace_bytes(B, T, n, r), dev, slot="smooth_gaps")
-    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
-    ob, ot, oj = out.stride()
-
-    def ptr(x):
-        return x.data_ptr() if x is not None else None
-
     _lib.check(lib.eks_smooth_gaps(
-        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
-        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(),
-        out.data_ptr(), ob, ot, oj, ptr(var), ptr(ms), ptr(Vs), ptr(nll_), nobs.data_ptr(),
-        ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)), "eks_smooth_gaps")
+        i.ptr, i.code, B, T, i.E, n, r, *i.strides, i.mode, params.data_ptr(), out.data_ptr(),
+        *out.stride(), _ptr(var), _ptr(ms), _ptr(Vs), _ptr(nll_), nobs.data_ptr(), ws.data_ptr(),
+        ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)), "eks_smooth_gaps")
     if check and B > 0:
-        bits = status_bits(status)
-        if bits & _lib.EKS_STATUS_SCAN:
-            raise ValueError("an observed column with zero ensemble variance: eks_smooth_gaps "
-                             "does not serve it")
-        if bits & _lib.EKS_STATUS_SINGULAR:
-            raise np.linalg.LinAlgError("Singular matrix")
+        _raise_on_status(status, "eks_smooth_gaps",
+                         _lib.EKS_STATUS_SCAN | _lib.EKS_STATUS_SINGULAR)
     return dict(out=out, var=var, Vs=Vs, ms=ms, nll=nll_, nobs=nobs, status=status)
 
 
@@ -839,15 +781,9 @@ def draws_gaps(obs, params, *, n: int, r: int, S=None, noise=None, seed=None,
     if (noise is None) == (seed is None):
         raise ValueError("draws_gaps needs exactly one of noise and seed")
     torch = _lib.require_gpu()
-    B, T, E, dt = _obs_code(obs, n)
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
-    yev = isinstance(obs, Yev)
-    if yev and mode != obs.mode:
-        raise ValueError("the hand-off planes were made in another averaging mode")
-    if params.shape != (B, param_len(n, r)) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({B}, {param_len(n, r)}) float64 tensor")
+    i = _member_input(obs, n, mode)
+    B, T = i.B, i.T
+    _check_params(params, B, n, r)
     if noise is not None:
         if noise.dim() != 4 or noise.shape[0] != B or noise.shape[2:] != (T, r) \
                 or noise.dtype != torch.float64 or (r > 1 and noise.stride(3) != 1):
@@ -869,30 +805,18 @@ def draws_gaps(obs, params, *, n: int, r: int, S=None, noise=None, seed=None,
     latent = torch.empty((B, S, T, r), **f64) if want_latent else None
     out = torch.empty((T, B, n), **f64).permute(1, 0, 2) if want_out or want_var else None
     var = torch.empty((T, B, n), **f64).permute(1, 0, 2) if want_var else None
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = _status_words(status, (B,), dev)
     lib = _lib.load()
     ws = workspace(lib.eks_draws_gaps_workspace_bytes(B, S, T, n, r), dev, slot="draws_gaps")
-    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
-    db, ds, dtt, dj = draws.stride()
     ob, ot, oj = out.stride() if out is not None else (0, 0, 0)
-
-    def ptr(x):
-        return x.data_ptr() if x is not None else None
-
     _lib.check(lib.eks_draws_gaps(
-        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
-        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(),
-        S, ptr(noise), zb, zs, zt, (int(seed) & (2 ** 64 - 1)) if seed is not None else 0,
-        draws_ptr, db, ds, dtt, dj, ptr(latent), ptr(out), ob, ot, oj, ptr(var),
+        i.ptr, i.code, B, T, i.E, n, r, *i.strides, i.mode, params.data_ptr(),
+        S, _ptr(noise), zb, zs, zt, (int(seed) & (2 ** 64 - 1)) if seed is not None else 0,
+        draws_ptr, *draws.stride(), _ptr(latent), _ptr(out), ob, ot, oj, _ptr(var),
         ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)), "eks_draws_gaps")
     if check and B > 0:
-        bits = status_bits(status)
-        if bits & _lib.EKS_STATUS_SCAN:
-            raise ValueError("an observed column with zero ensemble variance: eks_draws_gaps "
-                             "does not serve it")
-        if bits & _lib.EKS_STATUS_SINGULAR:
-            raise np.linalg.LinAlgError("Singular matrix")
+        _raise_on_status(status, "eks_draws_gaps",
+                         _lib.EKS_STATUS_SCAN | _lib.EKS_STATUS_SINGULAR)
     return dict(draws=draws, latent=latent, out=out if want_out else None, var=var, status=status)
 
 
@@ -916,41 +840,23 @@ def nll_sweep_gaps(obs, params, *, K: int, n: int, r: int, mode: str = "median",
     column with zero ensemble variance; there is no fallback path), and
     LinAlgError on EKS_STATUS_SINGULAR."""
     torch = _lib.require_gpu()
-    B, T, E, dt = _obs_code(obs, n)
-    if mode not in ("median", "mean"):
-        raise ValueError(f"{mode} averaging not supported")
-    yev = isinstance(obs, Yev)
-    if yev and mode != obs.mode:
-        raise ValueError("the hand-off planes were made in another averaging mode")
-    P = param_len(n, r)
-    if K < 0 or params.shape != (K * B, P) or params.dtype != torch.float64 \
-            or not params.is_contiguous():
-        raise ValueError(f"params must be a contiguous ({K * B}, {P}) float64 tensor")
+    i = _member_input(obs, n, mode)
+    B, T = i.B, i.T
+    _check_params(params, K * B, n, r, ok=K >= 0)
     dev = obs.device
     out = torch.empty((K, B), dtype=torch.float64, device=dev)
     nobs = torch.zeros((B,), dtype=torch.int32, device=dev)
-    if status is None:
-        status = torch.empty((K, B), dtype=torch.int32, device=dev)
-    elif status.shape != (K, B) or status.dtype != torch.int32 or not status.is_contiguous():
-        raise ValueError(f"status must be a contiguous ({K}, {B}) int32 tensor")
+    status = _status_words(status, (K, B), dev)
     lib = _lib.load()
     ws = workspace(lib.eks_nll_sweep_gaps_workspace_bytes(B, K, T, n, r), dev,
                    slot="nll_sweep_gaps")
-    sb, st, se, sj = (0, 0, 0, 0) if yev else obs.stride()
     _lib.check(lib.eks_nll_sweep_gaps(
-        obs.buf.data_ptr() if yev else obs.data_ptr(), dt, B, T, E, n, r, sb, st, se, sj,
-        _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN, params.data_ptr(), K,
-        out.data_ptr(), nobs.data_ptr(), ws.data_ptr(), ws.numel(), status.data_ptr(),
-        _lib.stream_ptr(stream)), "eks_nll_sweep_gaps")
+        i.ptr, i.code, B, T, i.E, n, r, *i.strides, i.mode, params.data_ptr(), K, out.data_ptr(),
+        nobs.data_ptr(), ws.data_ptr(), ws.numel(), status.data_ptr(), _lib.stream_ptr(stream)),
+        "eks_nll_sweep_gaps")
     if check and K * B > 0:
-        bits = status_bits(status)
-        if bits & _lib.EKS_STATUS_BAD_MODEL:
-            raise ValueError("the candidates of a trajectory must share C and offset")
-        if bits & _lib.EKS_STATUS_SCAN:
-            raise ValueError("an observed column with zero ensemble variance: "
-                             "eks_nll_sweep_gaps does not serve it")
-        if bits & _lib.EKS_STATUS_SINGULAR:
-            raise np.linalg.LinAlgError("Singular matrix")
+        _raise_on_status(status, "eks_nll_sweep_gaps", _lib.EKS_STATUS_BAD_MODEL
+                         | _lib.EKS_STATUS_SCAN | _lib.EKS_STATUS_SINGULAR)
     return dict(nll=out, nobs=nobs, status=status)
 
 
@@ -1008,39 +914,6 @@ def select_smooth_param(obs, params, *, n: int, r: int, mode: str = "median", gr
     Returns dict(smooth_param (B,), nll (B,), at_edge (B,) bool: the choice is
     the grid's first or last point, params (B, P): the rows with Q scaled;
     with ``allow_missing=True`` also nobs (B,) int32, the observed entries)."""
-    if allow_missing:
-        return _select_smooth_param_gaps(obs, params, n=n, r=r, mode=mode, grid=grid,
-                                         refine=refine)
-    torch = _lib.require_gpu()
-    B = params.shape[0]
-    dev = params.device
-    g0 = torch.as_tensor(DEFAULT_SWEEP_GRID if grid is None else np.asarray(grid, dtype=np.float64),
-                         dtype=torch.float64, device=dev)
-    if g0.dim() != 1 or g0.numel() < 1 or bool((g0[1:] <= g0[:-1]).any()) or bool((g0 <= 0).any()):
-        raise ValueError("grid must be a positive, strictly ascending 1-D sequence")
-    K = int(g0.numel())
-    g = g0.unsqueeze(0).repeat(B, 1)  # (B, K)
-    best_s = best_nll = None
-    for rnd in range(int(refine) + 1):
-        rows = scale_q(params, g.t().contiguous(), r=r)
-        scores = nll_sweep(obs, rows.view(K * B, -1), K=K, n=n, r=r, mode=mode).t()  # (B, K)
-        idx = torch.argmin(scores, dim=1)  # the first minimum: the smallest s
-        s = torch.gather(g, 1, idx.unsqueeze(1))[:, 0]
-        v = torch.gather(scores, 1, idx.unsqueeze(1))[:, 0]
-        if best_s is None:
-            best_s, best_nll = s, v
-        else:
-            better = v < best_nll
-            best_s = torch.where(better, s, best_s)
-            best_nll = torch.where(better, v, best_nll)
-        g = sweep_bracket(g, idx)
-    at_edge = (best_s == g0[0]) | (best_s == g0[-1])
-    return dict(smooth_param=best_s, nll=best_nll, at_edge=at_edge,
-                params=scale_q(params, best_s.unsqueeze(0), r=r)[0])
-
-
-def _select_smooth_param_gaps(obs, params, *, n: int, r: int, mode: str, grid, refine: int):
-    """``select_smooth_param`` with every round scored by ``nll_sweep_gaps``."""
     torch = _lib.require_gpu()
     B = params.shape[0]
     dev = params.device
@@ -1052,9 +925,12 @@ def _select_smooth_param_gaps(obs, params, *, n: int, r: int, mode: str, grid, r
     g = g0.unsqueeze(0).repeat(B, 1)  # (B, K)
     best_s = best_nll = nobs = None
     for rnd in range(int(refine) + 1):
-        rows = scale_q(params, g.t().contiguous(), r=r)
-        res = nll_sweep_gaps(obs, rows.view(K * B, -1), K=K, n=n, r=r, mode=mode)
-        scores, nobs = res["nll"].t(), res["nobs"]  # (B, K)
+        rows = scale_q(params, g.t().contiguous(), r=r).view(K * B, -1)
+        if allow_missing:
+            res = nll_sweep_gaps(obs, rows, K=K, n=n, r=r, mode=mode)
+            scores, nobs = res["nll"].t(), res["nobs"]  # (B, K)
+        else:
+            scores = nll_sweep(obs, rows, K=K, n=n, r=r, mode=mode).t()  # (B, K)
         idx = torch.argmin(scores, dim=1)  # the first minimum: the smallest s
         s = torch.gather(g, 1, idx.unsqueeze(1))[:, 0]
         v = torch.gather(scores, 1, idx.unsqueeze(1))[:, 0]
@@ -1066,8 +942,11 @@ def _select_smooth_param_gaps(obs, params, *, n: int, r: int, mode: str, grid, r
             best_nll = torch.where(better, v, best_nll)
         g = sweep_bracket(g, idx)
     at_edge = (best_s == g0[0]) | (best_s == g0[-1])
-    return dict(smooth_param=best_s, nll=best_nll, at_edge=at_edge,
-                params=scale_q(params, best_s.unsqueeze(0), r=r)[0], nobs=nobs)
+    res = dict(smooth_param=best_s, nll=best_nll, at_edge=at_edge,
+               params=scale_q(params, best_s.unsqueeze(0), r=r)[0])
+    if allow_missing:
+        res["nobs"] = nobs
+    return res
 
 
 def status_bits(status) -> int:

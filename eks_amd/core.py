@@ -90,13 +90,14 @@ def ensemble_handoff(stack, mode: str = "median", min_members=None):
     if code != _lib.EKS_YEV64:
         raise RuntimeError(f"eks_yev_dtype(F64) = {code}, expected EKS_YEV64")
     nbytes = lib.eks_yev_bytes(1, T, n, _lib.EKS_F64, E, m)
-    ev_off = (T * n * 8 + 255) // 256 * 256
     buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    if nbytes < ev_off + T * n * 8:
+    if nbytes < Yev.layout(1, T, n, code)[2]:
         raise RuntimeError("eks_yev_bytes smaller than the (T, n) y / ev planes")
+    yev = Yev(buf, 1, T, E, n, code, mode)
+    y, ev = yev.planes()  # (T, n, 1) views
     if min_members is None:
         _lib.check(lib.eks_ensemble(d.data_ptr(), _lib.EKS_F64, 1, T, E, n, 0, n, T * n, 1, m,
-                                    buf.data_ptr(), buf.data_ptr() + ev_off, _lib.stream_ptr()),
+                                    y.data_ptr(), ev.data_ptr(), _lib.stream_ptr()),
                    "eks_ensemble")
     else:
         if int(min_members) != min_members or not 1 <= min_members <= E:
@@ -105,10 +106,7 @@ def ensemble_handoff(stack, mode: str = "median", min_members=None):
                                          m, int(min_members), buf.data_ptr(), None,
                                          _lib.stream_ptr()),
                    "eks_ensemble_gaps")
-    planes = buf[:ev_off + T * n * 8]
-    preds = planes[:T * n * 8].view(torch.float64).reshape(T, n).cpu().numpy()
-    var = planes[ev_off:].view(torch.float64).reshape(T, n).cpu().numpy()
-    return Yev(buf, 1, T, E, n, code, mode), preds, var
+    return yev, y[:, :, 0].cpu().numpy(), ev[:, :, 0].cpu().numpy()
 
 
 def ensemble(markers_list, keys, mode: str = "median"):

@@ -12,7 +12,6 @@ long long g_draws_raw = 0;
 }
 
 namespace {
-bool dr_shape_ok(int n, int r) { return (r == 2 || r == 3) && n >= 1 && n <= kMaxObsRt; }
 constexpr long long kMaxDrawLanes = 1LL << 28;  // B * S: the 32-bit lane byte offset of a plane
 constexpr long long kMaxDrawT = 1LL << 40;      // the counter's time field
 }  // namespace
@@ -20,7 +19,7 @@ constexpr long long kMaxDrawT = 1LL << 40;      // the counter's time field
 extern "C" {
 
 size_t eks_draws_gaps_workspace_bytes(int64_t B, int64_t S, int64_t T, int n, int r) {
-  if (B <= 0 || S < 0 || T <= 0 || !dr_shape_ok(n, r)) return 0;
+  if (B <= 0 || S < 0 || T <= 0 || !chunked_shape_ok(n, r)) return 0;
   if (S > 0 && B > kMaxDrawLanes / S) return 0;
   const GpPlan g = gp_make_plan(B, T, r, gp_chunk_len(B, T, r));
   return dr_make_plan(g, B, S, T, n, r).total;
@@ -38,35 +37,21 @@ int eks_draws_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E, 
                    double *xdraws, double *out, int64_t ob, int64_t ot, int64_t oj, double *pvar,
                    void *workspace, size_t workspace_bytes, int32_t *status, void *stream) {
   clear_err();
-  if (!obs || !params || !draws || !status)
-    return set_err(EKS_ERR_ARG, "eks_draws_gaps: NULL pointer");
-  if (B < 0 || T < 1 || E < 1 || n < 1)
-    return set_err(EKS_ERR_ARG, "eks_draws_gaps: need B>=0, T>=1, E>=1, n>=1");
-  if (S < 0) return set_err(EKS_ERR_ARG, "eks_draws_gaps: need S>=0");
-  if (pvar && !out) return set_err(EKS_ERR_ARG, "eks_draws_gaps: pvar has out's strides, pass out");
-  if (obs_dtype != EKS_F32 && obs_dtype != EKS_F64 && obs_dtype != EKS_YEV32 &&
-      obs_dtype != EKS_YEV64)
-    return set_err(EKS_ERR_ARG, "eks_draws_gaps: bad dtype");
-  if (mode != EKS_MEDIAN && mode != EKS_MEAN)
-    return set_err(EKS_ERR_ARG, "eks_draws_gaps: bad mode");
-  if (E > kMaxMembers)
-    return set_err(EKS_ERR_UNSUPPORTED, "eks_draws_gaps: E=%d > %d", E, kMaxMembers);
-  if (!dr_shape_ok(n, r))
-    return set_err(EKS_ERR_UNSUPPORTED,
-                   "eks_draws_gaps: (r=%d, n=%d) not supported (r = 2 or 3, n <= %d)", r, n,
-                   kMaxObsRt);
+  const char *fn = "eks_draws_gaps";
+  const char *own = S < 0 ? "need S>=0" : pvar && !out ? "pvar has out's strides, pass out" : nullptr;
+  if (int rc = check_member_args(fn, obs && params && draws && status, B, T, E, n, r, obs_dtype,
+                                 mode, own))
+    return rc;
   if (T > kMaxDrawT || (S > 0 && B > kMaxDrawLanes / S))
     return set_err(EKS_ERR_UNSUPPORTED, "eks_draws_gaps: need B * S <= 2^28 and T <= 2^40");
   if (B == 0) return EKS_OK;
   const GpPlan p = gp_make_plan(B, T, r, gp_chunk_len(B, T, r));
   const DrPlan d = dr_make_plan(p, B, S, T, n, r);
-  if (!workspace || workspace_bytes < d.total)
-    return set_err(EKS_ERR_ARG, "eks_draws_gaps: workspace of %zu bytes needed", d.total);
+  if (int rc = check_workspace(fn, workspace, workspace_bytes, d.total)) return rc;
   hipStream_t s = (hipStream_t)stream;
   char *ws = (char *)workspace;
-  if (hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess ||
-      hipMemsetAsync(ws + d.bad_off, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess)
-    return set_err(EKS_ERR_HIP, "eks_draws_gaps: hipMemsetAsync(status) failed");
+  if (int rc = zero_status(fn, status, B, s)) return rc;
+  if (int rc = zero_status(fn, (int32_t *)(ws + d.bad_off), B, s)) return rc;
   // the smoother as eks_smooth_gaps runs it; ms_t stays in the workspace, and
   // out goes to workspace planes when the caller wants none
   GpArgs a{obs, obs_dtype, B,  T,  E,    n,   sb,      st,      se,      sj, mode == EKS_MEDIAN,

@@ -10,14 +10,10 @@ namespace eks {
 long long g_gaps_chunk = 0;
 }
 
-namespace {
-bool gp_shape_ok(int n, int r) { return (r == 2 || r == 3) && n >= 1 && n <= kMaxObsRt; }
-}  // namespace
-
 extern "C" {
 
 size_t eks_smooth_gaps_workspace_bytes(int64_t B, int64_t T, int n, int r) {
-  if (B <= 0 || T <= 0 || !gp_shape_ok(n, r)) return 0;
+  if (B <= 0 || T <= 0 || !chunked_shape_ok(n, r)) return 0;
   return gp_make_plan(B, T, r, gp_chunk_len(B, T, r)).total;
 }
 
@@ -32,28 +28,14 @@ int eks_smooth_gaps(const void *obs, int obs_dtype, int64_t B, int64_t T, int E,
                     double *Vs, double *nll, int32_t *nobs, void *workspace,
                     size_t workspace_bytes, int32_t *status, void *stream) {
   clear_err();
-  if (!obs || !params || !out || !status)
-    return set_err(EKS_ERR_ARG, "eks_smooth_gaps: NULL pointer");
-  if (B < 0 || T < 1 || E < 1 || n < 1)
-    return set_err(EKS_ERR_ARG, "eks_smooth_gaps: need B>=0, T>=1, E>=1, n>=1");
-  if (obs_dtype != EKS_F32 && obs_dtype != EKS_F64 && obs_dtype != EKS_YEV32 &&
-      obs_dtype != EKS_YEV64)
-    return set_err(EKS_ERR_ARG, "eks_smooth_gaps: bad dtype");
-  if (mode != EKS_MEDIAN && mode != EKS_MEAN)
-    return set_err(EKS_ERR_ARG, "eks_smooth_gaps: bad mode");
-  if (E > kMaxMembers)
-    return set_err(EKS_ERR_UNSUPPORTED, "eks_smooth_gaps: E=%d > %d", E, kMaxMembers);
-  if (!gp_shape_ok(n, r))
-    return set_err(EKS_ERR_UNSUPPORTED,
-                   "eks_smooth_gaps: (r=%d, n=%d) not supported (r = 2 or 3, n <= %d)", r, n,
-                   kMaxObsRt);
+  const char *fn = "eks_smooth_gaps";
+  if (int rc = check_member_args(fn, obs && params && out && status, B, T, E, n, r, obs_dtype, mode))
+    return rc;
   if (B == 0) return EKS_OK;
   const GpPlan p = gp_make_plan(B, T, r, gp_chunk_len(B, T, r));
-  if (!workspace || workspace_bytes < p.total)
-    return set_err(EKS_ERR_ARG, "eks_smooth_gaps: workspace of %zu bytes needed", p.total);
+  if (int rc = check_workspace(fn, workspace, workspace_bytes, p.total)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess)
-    return set_err(EKS_ERR_HIP, "eks_smooth_gaps: hipMemsetAsync(status) failed");
+  if (int rc = zero_status(fn, status, B, s)) return rc;
   const GpArgs a{obs, obs_dtype, B,  T,  E,    n,   sb,   st,  se,   sj,     mode == EKS_MEDIAN,
                  params, out,    ob, ot, oj,   pvar, ms,  Vs,  nll,  nobs,   (char *)workspace,
                  status, s};

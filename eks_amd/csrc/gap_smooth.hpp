@@ -98,18 +98,7 @@ inline int gp_map_len(int r) { return 2 * r * r + r + pv_sym_len(r); }  // GapMa
 // Chunk length as launched: pv_chunk_len's rule (a multiple of 8; one chunk
 // when it covers T) with its own debug key.
 inline long long gp_chunk_len(long long B, long long T, int r) {
-  long long L;
-  if (g_gaps_chunk > 0) {
-    L = round_up(g_gaps_chunk, 8);
-  } else {
-    L = call_chunk_len(B, T, r, true, 0);
-    if (!uniform_lanes(B) && B <= 256) {
-      const double c = r <= 2 ? 0.15 : 0.11;
-      L = std::max(L, round_up(std::llround(c * std::sqrt((double)T)), 8));
-    }
-  }
-  if (L >= T) L = round_up(T, 8);
-  return L;
+  return chunk_len_rule(g_gaps_chunk, call_chunk_len(B, T, r, true, 0), 0.15, 0.11, B, T, r);
 }
 
 inline GpPlan gp_make_plan(long long B, long long T, int r, long long L) {
@@ -117,12 +106,8 @@ inline GpPlan gp_make_plan(long long B, long long T, int r, long long L) {
   p.L = L;
   p.NC = (T + L - 1) / L;
   const size_t S = (size_t)pv_sym_len(r), R = (size_t)r, Bz = (size_t)B, NC = (size_t)p.NC;
-  size_t off = 0;
-  auto take = [&](size_t planes, size_t bytes) {
-    const size_t o = off;
-    off = align256(off + planes * Bz * bytes);
-    return o;
-  };
+  Carver ws;
+  auto take = [&](size_t planes, size_t bytes) { return ws.take(planes * Bz * bytes); };
   p.w_off = take((size_t)T * S, 8);
   p.sw_off = take((size_t)T * R, 8);
   p.kap_off = take((size_t)T, 8);
@@ -134,7 +119,7 @@ inline GpPlan gp_make_plan(long long B, long long T, int r, long long L) {
   p.bin_off = take(NC * (R + S), 8);
   p.nll_off = take(NC, 8);
   p.cnt_off = take(NC, 4);
-  p.total = off;
+  p.total = ws.off;
   return p;
 }
 
@@ -812,59 +797,33 @@ __global__ __launch_bounds__(kBlock) void k_gp_final(GpArgs a, GpPlan p) {
 template <int R>
 int launch_gp(const GpArgs &a, GpPlan p) {
   const bool uni = uniform_lanes(a.B);
-  const unsigned gch = uni ? (unsigned)(p.NC * blocks_per_chunk(a.B)) : grid_for(p.NC * a.B, kBlock);
-  const unsigned g64 = grid_for(a.B, 64);
+  const unsigned gch = lane_grid(p.NC, a.B);
   const bool wave_scan = p.NC > wave_scan_chunks();
-  const bool yev = a.dtype == EKS_YEV32 || a.dtype == EKS_YEV64;
-  if (yev)
-    p.evsrc = (const char *)a.obs + yev_ev_offset(a.B, a.T, a.n, a.dtype == EKS_YEV32 ? 4 : 8);
+  p.evsrc = yev_ev_planes(a.obs, a.dtype, a.B, a.T, a.n);
   int rc;
   prof_call_begin();
   prof_mark(a.stream, "k_gp_elem");
-  auto k1 = [&](auto ttag, auto Ec) -> int {
+  rc = dispatch_input(a.dtype, a.E, [&](auto ttag, auto Ec) -> int {
     using T = decltype(ttag);
     constexpr int EE = decltype(Ec)::value;
-    if (uni)
-      hipLaunchKernelGGL((k_gp_elem<R, T, EE, true>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
-    else
-      hipLaunchKernelGGL((k_gp_elem<R, T, EE, false>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
+    launch_uni(uni, k_gp_elem<R, T, EE, true>, k_gp_elem<R, T, EE, false>, gch, a.stream, a, p);
     return check_launch("k_gp_elem");
-  };
-  if (a.dtype == EKS_YEV32)
-    rc = k1(YevIn<float>{}, ic<0>{});
-  else if (a.dtype == EKS_YEV64)
-    rc = k1(YevIn<double>{}, ic<0>{});
-  else if (a.dtype == EKS_F32)
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(float{}, Ec); });
-  else
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(double{}, Ec); });
+  });
   if (rc) return rc;
   if (p.NC > 1) {
     prof_mark(a.stream, "k_gp_fscan");
-    if (!wave_scan)
-      hipLaunchKernelGGL((k_gp_fscan<R>), dim3(g64), dim3(64), 0, a.stream, a, p);
-    else
-      hipLaunchKernelGGL((k_gp_fscan_w<R>), dim3((unsigned)a.B), dim3(64), 0, a.stream, a, p);
+    launch_scan(wave_scan, k_gp_fscan<R>, k_gp_fscan_w<R>, a.B, a.stream, a, p);
     if ((rc = check_launch("k_gp_fscan"))) return rc;
   }
   prof_mark(a.stream, "k_gp_rerun");
-  if (uni)
-    hipLaunchKernelGGL((k_gp_rerun<R, true>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_gp_rerun<R, false>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
+  launch_uni(uni, k_gp_rerun<R, true>, k_gp_rerun<R, false>, gch, a.stream, a, p);
   if ((rc = check_launch("k_gp_rerun"))) return rc;
   // (a single chunk too: G4 writes nll and nobs)
   prof_mark(a.stream, "k_gp_bscan");
-  if (!wave_scan)
-    hipLaunchKernelGGL((k_gp_bscan<R>), dim3(g64), dim3(64), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_gp_bscan_w<R>), dim3((unsigned)a.B), dim3(64), 0, a.stream, a, p);
+  launch_scan(wave_scan, k_gp_bscan<R>, k_gp_bscan_w<R>, a.B, a.stream, a, p);
   if ((rc = check_launch("k_gp_bscan"))) return rc;
   prof_mark(a.stream, "k_gp_final");
-  if (uni)
-    hipLaunchKernelGGL((k_gp_final<R, true>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_gp_final<R, false>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
+  launch_uni(uni, k_gp_final<R, true>, k_gp_final<R, false>, gch, a.stream, a, p);
   prof_call_end(a.stream);
   return check_launch("k_gp_final");
 }

@@ -94,18 +94,8 @@ struct GsPlan {
 // (2176 x 10 000, uniform lanes) keeps the first rule's 176: 5.49 / 3.97 /
 // 3.06 / 2.94 / 2.92 at 32 / 64 / 128 / 176 / 200.
 inline long long gs_chunk_len(long long B, long long T, int r) {
-  long long L;
-  if (g_gaps_sweep_chunk > 0) {
-    L = round_up(g_gaps_sweep_chunk, 8);
-  } else {
-    L = 2 * call_chunk_len(B, T, r, false, 0);
-    if (!uniform_lanes(B) && B <= 256) {
-      const double c = r <= 2 ? 0.20 : 0.13;
-      L = std::max(L, round_up(std::llround(c * std::sqrt((double)T)), 8));
-    }
-  }
-  if (L >= T) L = round_up(T, 8);
-  return L;
+  return chunk_len_rule(g_gaps_sweep_chunk, 2 * call_chunk_len(B, T, r, false, 0), 0.20, 0.13, B, T,
+                        r);
 }
 
 inline GsPlan gs_make_plan(long long B, long long K, long long T, int r, long long L) {
@@ -114,11 +104,9 @@ inline GsPlan gs_make_plan(long long B, long long K, long long T, int r, long lo
   p.NC = (T + L - 1) / L;
   const size_t S = (size_t)pv_sym_len(r), R = (size_t)r, Bz = (size_t)B, KB = (size_t)(K * B),
                NC = (size_t)p.NC;
-  size_t off = 0;
+  Carver ws;
   auto take = [&](size_t planes, size_t width, size_t bytes) {
-    const size_t o = off;
-    off = align256(off + planes * width * bytes);
-    return o;
+    return ws.take(planes * width * bytes);
   };
   p.w_off = take((size_t)T * S, Bz, 8);
   p.sw_off = take((size_t)T * R, Bz, 8);
@@ -127,7 +115,7 @@ inline GsPlan gs_make_plan(long long B, long long K, long long T, int r, long lo
   p.sin_off = take(NC * (R + S), KB, 8);
   p.nll_off = take(NC, KB, 8);
   p.cnt_off = take(NC, Bz, 4);
-  p.total = off;
+  p.total = ws.off;
   return p;
 }
 
@@ -380,63 +368,36 @@ template <int R>
 int launch_gs(const GsArgs &a, GsPlan p) {
   const long long KB = a.K * a.B;
   const bool uni = uniform_lanes(a.B), uni_e = uniform_lanes(KB);
-  const unsigned g1 = uni ? (unsigned)(p.NC * blocks_per_chunk(a.B)) : grid_for(p.NC * a.B, kBlock);
-  const unsigned g2 = uni_e ? (unsigned)(p.NC * blocks_per_chunk(KB)) : grid_for(p.NC * KB, kBlock);
-  const unsigned g64 = grid_for(KB, 64);
+  const unsigned g1 = lane_grid(p.NC, a.B), g2 = lane_grid(p.NC, KB);
   const bool wave_scan = p.NC > wave_scan_chunks();
-  const bool yev = a.dtype == EKS_YEV32 || a.dtype == EKS_YEV64;
-  if (yev)
-    p.evsrc = (const char *)a.obs + yev_ev_offset(a.B, a.T, a.n, a.dtype == EKS_YEV32 ? 4 : 8);
+  p.evsrc = yev_ev_planes(a.obs, a.dtype, a.B, a.T, a.n);
   int rc;
   prof_call_begin();
   prof_mark(a.stream, "k_gs_reduce");
-  auto k1 = [&](auto ttag, auto Ec) -> int {
+  rc = dispatch_input(a.dtype, a.E, [&](auto ttag, auto Ec) -> int {
     using T = decltype(ttag);
     constexpr int EE = decltype(Ec)::value;
-    if (uni)
-      hipLaunchKernelGGL((k_gs_reduce<R, T, EE, true>), dim3(g1), dim3(kBlock), 0, a.stream, a, p);
-    else
-      hipLaunchKernelGGL((k_gs_reduce<R, T, EE, false>), dim3(g1), dim3(kBlock), 0, a.stream, a, p);
+    launch_uni(uni, k_gs_reduce<R, T, EE, true>, k_gs_reduce<R, T, EE, false>, g1, a.stream, a, p);
     return check_launch("k_gs_reduce");
-  };
-  if (a.dtype == EKS_YEV32)
-    rc = k1(YevIn<float>{}, ic<0>{});
-  else if (a.dtype == EKS_YEV64)
-    rc = k1(YevIn<double>{}, ic<0>{});
-  else if (a.dtype == EKS_F32)
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(float{}, Ec); });
-  else
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(double{}, Ec); });
+  });
   if (rc) return rc;
   if (p.NC == 1) {
     prof_mark(a.stream, "k_gs_seq");
-    hipLaunchKernelGGL((k_gs_seq<R>), dim3(g64), dim3(64), 0, a.stream, a, p);
+    hipLaunchKernelGGL((k_gs_seq<R>), dim3(grid_for(KB, 64)), dim3(64), 0, a.stream, a, p);
     prof_call_end(a.stream);
     return check_launch("k_gs_seq");
   }
   prof_mark(a.stream, "k_gs_elem");
-  if (uni_e)
-    hipLaunchKernelGGL((k_gs_elem<R, true>), dim3(g2), dim3(kBlock), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_gs_elem<R, false>), dim3(g2), dim3(kBlock), 0, a.stream, a, p);
+  launch_uni(uni_e, k_gs_elem<R, true>, k_gs_elem<R, false>, g2, a.stream, a, p);
   if ((rc = check_launch("k_gs_elem"))) return rc;
   prof_mark(a.stream, "k_gs_fscan");
-  if (!wave_scan)
-    hipLaunchKernelGGL((k_gs_fscan<R>), dim3(g64), dim3(64), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_gs_fscan_w<R>), dim3((unsigned)KB), dim3(64), 0, a.stream, a, p);
+  launch_scan(wave_scan, k_gs_fscan<R>, k_gs_fscan_w<R>, KB, a.stream, a, p);
   if ((rc = check_launch("k_gs_fscan"))) return rc;
   prof_mark(a.stream, "k_gs_share");
-  if (uni_e)
-    hipLaunchKernelGGL((k_gs_share<R, true>), dim3(g2), dim3(kBlock), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_gs_share<R, false>), dim3(g2), dim3(kBlock), 0, a.stream, a, p);
+  launch_uni(uni_e, k_gs_share<R, true>, k_gs_share<R, false>, g2, a.stream, a, p);
   if ((rc = check_launch("k_gs_share"))) return rc;
   prof_mark(a.stream, "k_gs_sum");
-  if (!wave_scan)
-    hipLaunchKernelGGL(k_gs_sum, dim3(g64), dim3(64), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL(k_gs_sum_w, dim3((unsigned)KB), dim3(64), 0, a.stream, a, p);
+  launch_scan(wave_scan, k_gs_sum, k_gs_sum_w, KB, a.stream, a, p);
   prof_call_end(a.stream);
   return check_launch("k_gs_sum");
 }

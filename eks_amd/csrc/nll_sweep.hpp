@@ -51,7 +51,7 @@
 // bitwise from candidate 0's.  A singular step (innovation variance <= 0, a
 // singular I + P J of a composition) sets EKS_STATUS_SINGULAR.
 #pragma once
-#include "smooth_impl.hpp"
+#include "host_api.hpp"
 
 namespace eks {
 
@@ -95,25 +95,19 @@ inline int sw_row_len(int r) { return r * (r + 3) / 2; }
 // L = 16 / 32 / 64 / 128; 17 x 50 000, (3,8): 0.94 / 0.86 / 0.93 at 16 / 32 /
 // 64; the shard: 2.91 / 2.23 / 2.20 at 64 / 128 / 256).
 inline long long sw_chunk_len(long long B, long long T, int r) {
-  long long L = g_sweep_chunk > 0 ? round_up(g_sweep_chunk, 8) : 2 * call_chunk_len(B, T, r, false, 0);
-  if (L >= T) L = round_up(T, 8);
-  return L;
+  return chunk_len_rule(g_sweep_chunk, 2 * call_chunk_len(B, T, r, false, 0), 0, 0, B, T, r);
 }
 
 inline SwPlan sw_make_plan(long long B, long long K, long long T, int r, long long L) {
   SwPlan p;
   p.L = L;
   p.NC = (T + L - 1) / L;
-  size_t off = 0;
-  auto take = [&](size_t doubles) {
-    const size_t o = off;
-    off = align256(off + doubles * 8);
-    return o;
-  };
+  Carver ws;
+  auto take = [&](size_t doubles) { return ws.take(doubles * 8); };
   p.row_off = take((size_t)T * (size_t)B * (size_t)sw_row_len(r));
   p.elem_off = take((size_t)p.NC * (size_t)K * (size_t)B * (size_t)(elem_len(r) + 1));
   p.kap_off = take((size_t)p.NC * (size_t)B);
-  p.total = off;
+  p.total = ws.off;
   return p;
 }
 
@@ -509,31 +503,17 @@ template <int R>
 int launch_sw(const SwArgs &a, SwPlan p) {
   const long long KB = a.K * a.B;
   const bool uni = uniform_lanes(a.B), uni_e = uniform_lanes(KB);
-  const unsigned g1 = uni ? (unsigned)(p.NC * blocks_per_chunk(a.B)) : grid_for(p.NC * a.B, kBlock);
-  const unsigned g2 = uni_e ? (unsigned)(p.NC * blocks_per_chunk(KB)) : grid_for(p.NC * KB, kBlock);
-  const bool yev = a.dtype == EKS_YEV32 || a.dtype == EKS_YEV64;
-  if (yev)
-    p.evsrc = (const char *)a.obs + yev_ev_offset(a.B, a.T, a.n, a.dtype == EKS_YEV32 ? 4 : 8);
+  const unsigned g1 = lane_grid(p.NC, a.B), g2 = lane_grid(p.NC, KB);
+  p.evsrc = yev_ev_planes(a.obs, a.dtype, a.B, a.T, a.n);
   int rc;
   prof_call_begin();
   prof_mark(a.stream, "k_sw_reduce");
-  auto k1 = [&](auto ttag, auto Ec) -> int {
+  rc = dispatch_input(a.dtype, a.E, [&](auto ttag, auto Ec) -> int {
     using T = decltype(ttag);
     constexpr int EE = decltype(Ec)::value;
-    if (uni)
-      hipLaunchKernelGGL((k_sw_reduce<R, T, EE, true>), dim3(g1), dim3(kBlock), 0, a.stream, a, p);
-    else
-      hipLaunchKernelGGL((k_sw_reduce<R, T, EE, false>), dim3(g1), dim3(kBlock), 0, a.stream, a, p);
+    launch_uni(uni, k_sw_reduce<R, T, EE, true>, k_sw_reduce<R, T, EE, false>, g1, a.stream, a, p);
     return check_launch("k_sw_reduce");
-  };
-  if (a.dtype == EKS_YEV32)
-    rc = k1(YevIn<float>{}, ic<0>{});
-  else if (a.dtype == EKS_YEV64)
-    rc = k1(YevIn<double>{}, ic<0>{});
-  else if (a.dtype == EKS_F32)
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(float{}, Ec); });
-  else
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(double{}, Ec); });
+  });
   if (rc) return rc;
   if (p.NC == 1) {
     prof_mark(a.stream, "k_sw_seq");
@@ -542,16 +522,10 @@ int launch_sw(const SwArgs &a, SwPlan p) {
     return check_launch("k_sw_seq");
   }
   prof_mark(a.stream, "k_sw_elem");
-  if (uni_e)
-    hipLaunchKernelGGL((k_sw_elem<R, true>), dim3(g2), dim3(kBlock), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_sw_elem<R, false>), dim3(g2), dim3(kBlock), 0, a.stream, a, p);
+  launch_uni(uni_e, k_sw_elem<R, true>, k_sw_elem<R, false>, g2, a.stream, a, p);
   if ((rc = check_launch("k_sw_elem"))) return rc;
   prof_mark(a.stream, "k_sw_scan");
-  if (p.NC <= wave_scan_chunks())
-    hipLaunchKernelGGL((k_sw_scan<R>), dim3(grid_for(KB, 64)), dim3(64), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_sw_scan_w<R>), dim3((unsigned)KB), dim3(64), 0, a.stream, a, p);
+  launch_scan(p.NC > wave_scan_chunks(), k_sw_scan<R>, k_sw_scan_w<R>, KB, a.stream, a, p);
   prof_call_end(a.stream);
   return check_launch("k_sw_scan");
 }

@@ -47,7 +47,7 @@
 // NaN and with it every value of the trajectory.  A NaN ev propagates the same
 // way and is not an error.
 #pragma once
-#include "smooth_impl.hpp"
+#include "host_api.hpp"
 
 namespace eks {
 
@@ -93,18 +93,7 @@ inline int pv_sym_len(int r) { return r * (r + 1) / 2; }
 // 0.43 -> 0.25 ms; T = 50 000, r = 3, n = 8: L = 32, 0.59 -> 0.55 ms;
 // tools/pvar_timing.py --chunk).
 inline long long pv_chunk_len(long long B, long long T, int r) {
-  long long L;
-  if (g_pvar_chunk > 0) {
-    L = round_up(g_pvar_chunk, 8);
-  } else {
-    L = call_chunk_len(B, T, r, true, 0);
-    if (!uniform_lanes(B) && B <= 256) {
-      const double c = r <= 2 ? 0.15 : 0.11;
-      L = std::max(L, round_up(std::llround(c * std::sqrt((double)T)), 8));
-    }
-  }
-  if (L >= T) L = round_up(T, 8);
-  return L;
+  return chunk_len_rule(g_pvar_chunk, call_chunk_len(B, T, r, true, 0), 0.15, 0.11, B, T, r);
 }
 
 inline PvPlan pv_make_plan(long long B, long long T, int r, long long L) {
@@ -112,19 +101,15 @@ inline PvPlan pv_make_plan(long long B, long long T, int r, long long L) {
   p.L = L;
   p.NC = (T + L - 1) / L;
   const size_t S = (size_t)pv_sym_len(r), RR = (size_t)r * r, Bz = (size_t)B;
-  size_t off = 0;
-  auto take = [&](size_t doubles) {
-    const size_t o = off;
-    off = align256(off + doubles * Bz * 8);
-    return o;
-  };
+  Carver ws;
+  auto take = [&](size_t doubles) { return ws.take(doubles * Bz * 8); };
   p.w_off = take((size_t)T * S);
   p.p_off = take((size_t)T * S);
   p.elem_off = take((size_t)p.NC * (RR + 2 * S));
   p.pin_off = take((size_t)p.NC * S);
   p.map_off = take((size_t)p.NC * (RR + S));
   p.vin_off = take((size_t)p.NC * S);
-  p.total = off;
+  p.total = ws.off;
   return p;
 }
 
@@ -828,58 +813,35 @@ __global__ __launch_bounds__(kBlock) void k_pv_final(PvArgs a, PvPlan p) {
 template <int R>
 int launch_pv(const PvArgs &a, PvPlan p) {
   const bool uni = uniform_lanes(a.B);
-  const unsigned gch = uni ? (unsigned)(p.NC * blocks_per_chunk(a.B)) : grid_for(p.NC * a.B, kBlock);
-  const unsigned g64 = grid_for(a.B, 64);
+  const unsigned gch = lane_grid(p.NC, a.B);
   const bool wave_scan = p.NC > wave_scan_chunks();
-  const bool yev = a.dtype == EKS_YEV32 || a.dtype == EKS_YEV64;
-  if (yev)
-    p.evsrc = (const char *)a.obs + yev_ev_offset(a.B, a.T, a.n, a.dtype == EKS_YEV32 ? 4 : 8);
+  p.evsrc = yev_ev_planes(a.obs, a.dtype, a.B, a.T, a.n);
   int rc;
   prof_call_begin();
   prof_mark(a.stream, "k_pv_elem");
-  auto k1 = [&](auto ttag, auto Ec) -> int {
+  // (a hand-off: only the ev planes are read)
+  rc = dispatch_input<false>(a.dtype, a.E, [&](auto ttag, auto Ec) -> int {
     using T = decltype(ttag);
     constexpr int EE = decltype(Ec)::value;
-    if (uni)
-      hipLaunchKernelGGL((k_pv_elem<R, T, EE, true>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
-    else
-      hipLaunchKernelGGL((k_pv_elem<R, T, EE, false>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
+    launch_uni(uni, k_pv_elem<R, T, EE, true>, k_pv_elem<R, T, EE, false>, gch, a.stream, a, p);
     return check_launch("k_pv_elem");
-  };
-  if (yev)
-    rc = k1(YevIn<double>{}, ic<0>{});  // only the ev planes are read
-  else if (a.dtype == EKS_F32)
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(float{}, Ec); });
-  else
-    rc = dispatch_members_c(a.E, [&](auto Ec) { return k1(double{}, Ec); });
+  });
   if (rc) return rc;
   if (p.NC > 1) {
     prof_mark(a.stream, "k_pv_fscan");
-    if (!wave_scan)
-      hipLaunchKernelGGL((k_pv_fscan<R>), dim3(g64), dim3(64), 0, a.stream, a, p);
-    else
-      hipLaunchKernelGGL((k_pv_fscan_w<R>), dim3((unsigned)a.B), dim3(64), 0, a.stream, a, p);
+    launch_scan(wave_scan, k_pv_fscan<R>, k_pv_fscan_w<R>, a.B, a.stream, a, p);
     if ((rc = check_launch("k_pv_fscan"))) return rc;
   }
   prof_mark(a.stream, "k_pv_rerun");
-  if (uni)
-    hipLaunchKernelGGL((k_pv_rerun<R, true>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_pv_rerun<R, false>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
+  launch_uni(uni, k_pv_rerun<R, true>, k_pv_rerun<R, false>, gch, a.stream, a, p);
   if ((rc = check_launch("k_pv_rerun"))) return rc;
   if (p.NC > 1) {
     prof_mark(a.stream, "k_pv_bscan");
-    if (!wave_scan)
-      hipLaunchKernelGGL((k_pv_bscan<R>), dim3(g64), dim3(64), 0, a.stream, a, p);
-    else
-      hipLaunchKernelGGL((k_pv_bscan_w<R>), dim3((unsigned)a.B), dim3(64), 0, a.stream, a, p);
+    launch_scan(wave_scan, k_pv_bscan<R>, k_pv_bscan_w<R>, a.B, a.stream, a, p);
     if ((rc = check_launch("k_pv_bscan"))) return rc;
   }
   prof_mark(a.stream, "k_pv_final");
-  if (uni)
-    hipLaunchKernelGGL((k_pv_final<R, true>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
-  else
-    hipLaunchKernelGGL((k_pv_final<R, false>), dim3(gch), dim3(kBlock), 0, a.stream, a, p);
+  launch_uni(uni, k_pv_final<R, true>, k_pv_final<R, false>, gch, a.stream, a, p);
   prof_call_end(a.stream);
   return check_launch("k_pv_final");
 }

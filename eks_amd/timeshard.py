@@ -45,34 +45,17 @@ class Segment:
                  mode: str = "median", flags: int = 0, out=None, slot: str = "seg0",
                  want_out: bool = True, want_ms: bool = False):
         torch = _lib.require_gpu()
-        if isinstance(obs, batch.Yev):
-            B, T, E, nn = obs.shape
-            self.dt, self.ptr, self.strides = obs.code, obs.buf.data_ptr(), (0, 0, 0, 0)
-            if mode != obs.mode:
-                raise ValueError("the hand-off planes were made in another averaging mode")
-        else:
-            if obs.dim() != 4:
-                raise ValueError("obs must be viewed as (B, T, E, n)")
-            B, T, E, nn = obs.shape
-            if obs.dtype not in (torch.float32, torch.float64):
-                raise TypeError("obs must be float32 or float64")
-            self.dt = _lib.EKS_F32 if obs.dtype == torch.float32 else _lib.EKS_F64
-            self.ptr, self.strides = obs.data_ptr(), obs.stride()
-        if nn != n:
-            raise ValueError(f"obs has {nn} coordinates, expected n={n}")
-        if mode not in ("median", "mean"):
-            raise ValueError(f"{mode} averaging not supported")
-        if params.shape != (B, batch.param_len(n, r)) or params.dtype != torch.float64 \
-                or not params.is_contiguous():
-            raise ValueError(f"params must be a contiguous ({B}, {batch.param_len(n, r)}) "
-                             "float64 tensor")
+        i = batch._member_input(obs, n, mode)
+        B, T, E = i.B, i.T, i.E
+        self.dt, self.ptr, self.strides = i.code, i.ptr, i.strides
+        batch._check_params(params, B, n, r)
         if not 0 <= t_base <= T_total - T:
             raise ValueError(f"frames [{t_base}, {t_base + T}) outside [0, {T_total})")
         dev = params.device
         self.obs, self.params = obs, params  # keep the buffers alive across phases
         self.B, self.T, self.E, self.n, self.r = B, T, E, n, r
         self.t_base, self.T_total, self.flags = t_base, T_total, flags
-        self.mode = _lib.EKS_MEDIAN if mode == "median" else _lib.EKS_MEAN
+        self.mode = i.mode
         if want_out and out is None:
             out = torch.empty((T, B, n), dtype=torch.float64, device=dev).permute(1, 0, 2)
         self.out = out if want_out else None  # None: filter only (NLL), phases 1-2

@@ -41,6 +41,51 @@ def test_meta_shapes():
                                         m(8, 3, dt=f8), m(3, 3, dt=f8), 1)
     assert q.shape == (3, 40, 3)
     assert torch.ops.eks.interp1d(m(10, dt=f8), m(10, 4, dt=f8), m(7, dt=f8)).shape == (7, 4)
+    _member_op_meta_shapes(2, 2)
+    _member_op_meta_shapes(8, 3)
+
+
+def _member_op_meta_shapes(n, r):
+    """Shape, dtype and contiguity of every output of the nine later operators
+    at B=3, T=5, E=4, K=2, S=2."""
+    import eks_amd.ops  # noqa: F401
+    from eks_amd import _lib
+    lib = _lib.load()
+    B, T, E, K, S = 3, 5, 4, 2, 2
+    f4, f8, i4, u1 = torch.float32, torch.float64, torch.int32, torch.uint8
+    m = lambda *s, dt=f8: torch.empty(s, device="meta", dtype=dt)  # noqa: E731
+    P = lib.eks_param_len(n, r)
+    obs, prm, rows = m(B, T, E, n, dt=f4), m(B, P), m(K * B, P)
+    eks = torch.ops.eks
+    yev32 = lib.eks_yev_bytes(B, T, n, _lib.EKS_F32, E, _lib.EKS_MEDIAN)
+    yev64 = lib.eks_yev_bytes(B, T, n, _lib.EKS_F64, E, _lib.EKS_MEDIAN)
+    cases = {
+        "smooth_var": (eks.smooth_var(obs, prm, n, r),
+                       [((B, T, n), f8), ((B, T, r, r), f8), ((B,), i4)]),
+        "smooth_gaps": (eks.smooth_gaps(obs, prm, n, r, "median"),
+                        [((B, T, n), f8), ((B, T, n), f8), ((B,), f8), ((B,), i4), ((B,), i4)]),
+        "draws_gaps": (eks.draws_gaps(obs, prm, m(B, S, T, r), n, r, "median"),
+                       [((B, S, T, n), f8), ((B, S, T, r), f8), ((B, T, n), f8), ((B,), i4)]),
+        "draws_noise": ((eks.draws_noise(obs, B, S, T, r, 7),), [((B, S, T, r), f8)]),
+        "nll_sweep": (eks.nll_sweep(obs, rows, K, n, r, "median"), [((K, B), f8), ((K, B), i4)]),
+        "nll_sweep_gaps": (eks.nll_sweep_gaps(obs, rows, K, n, r, "median"),
+                           [((K, B), f8), ((B,), i4), ((K, B), i4)]),
+        "fit_gaps": (eks.fit_gaps(obs, "multicam" if n > r else "singleview", n, r, 1.0, 25.0,
+                                  "median"),
+                     [((B, P), f8), ((B,), i4), ((yev32,), u1), ((B,), i4), ((B,), i4)]),
+        "ensemble_gaps": (eks.ensemble_gaps(obs, "median", 2), [((yev64,), u1), ((T, n, B), u1)]),
+    }
+    if n == 8:
+        cases["fit_pupil"] = (eks.fit_pupil(obs, "median"),
+                              [((B, 6), f8), ((B,), i4), ((B,), i4), ((yev64,), u1)])
+    else:  # the pupil model has 8 coordinates: another n is refused by the Meta kernel too
+        with pytest.raises(RuntimeError, match="obs must be viewed as"):
+            eks.fit_pupil(obs, "median")
+    for name, (outs, want) in cases.items():
+        assert len(outs) == len(want), name
+        for k, (t, (shape, dt)) in enumerate(zip(outs, want)):
+            assert t.device.type == "meta" and tuple(t.shape) == shape and t.dtype == dt, (name, k)
+            assert t.is_contiguous(), (name, k)
 
 
 def test_cpu_tensor_is_a_dispatch_error():
