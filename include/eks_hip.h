@@ -31,6 +31,8 @@
  *       EKS_STATUS_SCAN       the time-parallel scan could not form a chunk
  *                             summary (singular Q with exact observations);
  *                             rerun that batch with algo = 1
+ *     More than r exact columns in one frame is the reference's singular S.
+ *     It is flagged only when a pivot rounds to <= 0.
  *     NaNs propagate exactly as in numpy and are not an error.
  */
 #ifndef EKS_HIP_H
